@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """Headline benchmark: q-means Lloyd-iteration throughput on 10M x 256,
-k = 1024, row-sharded over N MI355X GPUs (BASELINE.json config 3), plus the
-q-means fit wall-clock and the qPCA wall-clocks (configs 2/5) as extras.
+k = 1024, row-sharded over N MI355X GPUs (BASELINE.json config 3).  A plain
+run sets up, warms up, times ``--steps`` steps and prints the result line;
+``--full`` adds everything else the benchmark measures as extras of that
+line: per-phase and unpruned / first-iteration times, the N = 8 share, the
+IPE distance mode, the overlapping-blobs regime, the 70k x 784 shape, the
+q-means fit wall-clocks, the qPCA wall-clocks (configs 2/5) and the qPCA ->
+q-means pipeline.
 
 One step = one full q-means iteration of the reference's delta-means path
 (``_dmeans.py:534-671`` with ``delta > 0``, ``true_distance_estimate=False``,
@@ -17,9 +22,17 @@ Nothing is skipped inside the timed region.
 Strong scaling: the 10M rows are split across ranks (each rank generates its
 own shard in HBM from the global Philox stream - same dataset for every N).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
     (N > 1 without torchrun: re-launched under torch.distributed.run, one
      process per GPU, before any GPU call)
+
+``--dump-outputs DIR`` writes what the last timed step returned to its caller
+as ``DIR/<name>.npy``: ``labels`` (float32; a fixed seeded sample of the rows,
+with ``label_rows`` holding their indices, when there are more than
+``DUMP_MAX_LABELS``), ``centers`` (float32) and ``scalars`` (float64, the
+step's convergence read-back).  The data, the initial centres and every
+Philox key derive from ``--seed``, so the same arguments give the same inputs
+in every run.
 """
 
 import argparse
@@ -34,6 +47,8 @@ import numpy as np
 import torch
 
 BASELINE_SAMPLES_PER_S = 3.7e3   # reference q-means iteration, 8-core Xeon
+DUMP_MAX_LABELS = 12_000_000     # --dump-outputs: labels written whole up to here (48 MB) ...
+DUMP_SAMPLE_LABELS = 4_000_000   # ... beyond it this many sampled rows (16 MB + 32 MB of indices)
 
 
 def parse(argv=None):
@@ -64,6 +79,13 @@ def parse(argv=None):
     ap.add_argument("--no-pipeline", action="store_true",
                     help="skip the qPCA -> q-means pipeline (config 5) extra")
     ap.add_argument("--pipeline-rows", type=int, default=50_000_000)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every extra measurement (phases, "
+                         "unpruned / first iteration, N = 8 share, IPE, hard regime, 70k x 784, "
+                         "fit and qPCA wall-clocks, pipeline); the --no-* and --ipe-* options "
+                         "select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's labels, centres and scalars as DIR/*.npy")
     return ap.parse_args(argv)
 
 
@@ -437,6 +459,61 @@ def _fit_extra(extra, a, sa, comm, dev, init, ipe=False, name=None, n_init=1):
         extra[name + "_error"] = repr(e)[:200]
 
 
+def _dump_outputs(a, comm, labels, scalars, centers):
+    """--dump-outputs: the last timed step's outputs as ``DIR/<name>.npy``.
+    Rank 0 writes the (replicated) centres and scalars; every rank its own
+    rows' labels (``labels``, or ``labels_rank<r>`` on more than one GPU)."""
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    world = comm.world_size
+    tag = "" if world == 1 else f"_rank{comm.rank}"
+    m = labels.shape[0]
+    if m > DUMP_MAX_LABELS // world:
+        rows = np.sort(np.random.RandomState(a.seed + comm.rank).choice(
+            m, DUMP_SAMPLE_LABELS // world, replace=False))
+        labels = labels[torch.as_tensor(rows, device=labels.device)]
+        np.save(os.path.join(a.dump_outputs, f"label_rows{tag}.npy"), rows.astype(np.float64))
+    np.save(os.path.join(a.dump_outputs, f"labels{tag}.npy"),
+            labels.cpu().numpy().astype(np.float32))
+    if comm.rank == 0:
+        np.save(os.path.join(a.dump_outputs, "centers.npy"),
+                centers.float().cpu().numpy().astype(np.float32))
+        np.save(os.path.join(a.dump_outputs, "scalars.npy"), np.asarray(scalars, dtype=np.float64))
+
+
+def _finish(a, comm, value, ms_per_step, extra):
+    """Print the result line (rank 0) and leave the process group."""
+    if comm.rank == 0:
+        out = {
+            "metric": "q-means fit samples/sec (Lloyd samples*iterations/s, delta-means + tomography noise)",
+            "value": value,
+            "unit": "samples*iter/s",
+            "n_gpus": comm.world_size,
+            "steps": a.steps,
+            "warmup": a.warmup,
+            "ms_per_step": ms_per_step,
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": value / BASELINE_SAMPLES_PER_S,
+            "dtype": a.dtype,
+            "data": f"synthetic (on-device make_blobs, Philox-keyed, {a.blobs} blobs)",
+            "config": {"model": f"q-means k={a.k} delta={a.delta} ({a.n} x {a.d} synthetic)",
+                       "global_batch": a.n, "seq_len": a.d,
+                       "parallelism": f"dp{comm.world_size}"},
+            "extra": extra,
+        }
+        if "ipe_samples_iter_per_s" in extra:
+            # the reference's DEFAULT distance mode (true_distance_estimate=True)
+            out["co_headline"] = {
+                "metric": "q-means IPE (true_distance_estimate) samples*iter/s",
+                "value": extra["ipe_samples_iter_per_s"], "unit": "samples*iter/s",
+                "ms_per_step": extra.get("ipe_ms_per_step")}
+        print(json.dumps(out), flush=True)
+    if comm.distributed:
+        import torch.distributed as dist
+        dist.destroy_process_group()
+    return 0
+
+
 def main(argv=None):
     a = parse(argv)
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
@@ -474,8 +551,11 @@ def main(argv=None):
                       gemm_precision=a.dtype)
     eng.set_centers(C0)
 
+    out_labels = None
+
     def step():
-        labels, sc = eng.step()
+        nonlocal out_labels
+        out_labels, sc = eng.step()
         return sc.tolist()          # convergence read-back, as in fit()
 
     # as in QMeans.fit: the next iteration's E-step is enqueued before the
@@ -502,6 +582,11 @@ def main(argv=None):
                            if a.dtype == "fp32" else "bf16 operands (approximate band edges)")}
     eng.pipeline = False
     eng.drop_pending()
+    if a.dump_outputs:
+        _dump_outputs(a, comm, out_labels, last, eng.centers())
+    if not a.full:
+        return _finish(a, comm, value, ms_per_step, extra)
+    # --full: everything below is extra measurement behind the headline figure
     if eng.fast and gpu:
         cnt = eng.buf.counts.tolist()
         extra["overflow_rows_last"], extra["dense_rows_last"] = int(cnt[0]), int(cnt[1])
@@ -595,37 +680,7 @@ def main(argv=None):
         torch.cuda.empty_cache()
     if gpu and not a.no_pipeline:
         _pipeline_extra(extra, a, comm, dev)
-
-    if rank == 0:
-        out = {
-            "metric": "q-means fit samples/sec (Lloyd samples*iterations/s, delta-means + tomography noise)",
-            "value": value,
-            "unit": "samples*iter/s",
-            "n_gpus": comm.world_size,
-            "steps": a.steps,
-            "warmup": a.warmup,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": value / BASELINE_SAMPLES_PER_S,
-            "dtype": a.dtype,
-            "data": f"synthetic (on-device make_blobs, Philox-keyed, {a.blobs} blobs)",
-            "config": {"model": f"q-means k={a.k} delta={a.delta} ({a.n} x {a.d} synthetic)",
-                       "global_batch": a.n, "seq_len": a.d,
-                       "parallelism": f"dp{comm.world_size}"},
-            "extra": extra,
-        }
-        if "ipe_samples_iter_per_s" in extra:
-            # the reference's DEFAULT distance mode (true_distance_estimate=True)
-            out["co_headline"] = {
-                "metric": "q-means IPE (true_distance_estimate) samples*iter/s",
-                "value": extra["ipe_samples_iter_per_s"], "unit": "samples*iter/s",
-                "ms_per_step": extra.get("ipe_ms_per_step")}
-        print(json.dumps(out), flush=True)
-    if comm.distributed:
-        import torch.distributed as dist
-        dist.destroy_process_group()
-    return 0
+    return _finish(a, comm, value, ms_per_step, extra)
 
 
 if __name__ == "__main__":

@@ -5,7 +5,7 @@
 for rows in 1250000 10000000; do
   for v in "$@"; do
     if [ "$v" = cur ]; then unset SQ_NATIVE_VARIANT; else export SQ_NATIVE_VARIANT=$v; fi
-    out=$(timeout -k 10 150 python bench.py --rows $rows --no-fit --no-qpca --ipe-steps 0 2>/dev/null)
+    out=$(timeout -k 10 150 python bench.py --full --rows $rows --no-fit --no-qpca --ipe-steps 0 2>/dev/null)
     rc=$?
     if [ $rc -ne 0 ]; then echo "$v rows=$rows rc=$rc"; exit $rc; fi
     echo "$v rows=$rows $(echo "$out" | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(round(d["ms_per_step"],4), d["extra"]["phase_ms"], d["extra"]["inertia_last"])')"

@@ -1,4 +1,4 @@
-"""Per-step GPU kernel time in the timed window of a bench.py run under
+"""Per-step GPU kernel time in the timed window of a bench.py --full run under
 rocprofv3 --kernel-trace: the last STEPS steps, delimited by the certified
 E-step launches.  usage: scripts/step_kernels.py DB [STEPS] [TOP]"""
 import sqlite3
@@ -9,7 +9,7 @@ steps = int(sys.argv[2]) if len(sys.argv) > 2 else 20
 top = int(sys.argv[3]) if len(sys.argv) > 3 else 16
 rows = sqlite3.connect(db).execute("select name, start, end from kernels order by start").fetchall()
 x = [i for i, r in enumerate(rows) if "estep_x64" in r[0]]
-# bench.py: warmup + STEPS timed + 3 phase-timed steps after them
+# bench.py --full: warmup + STEPS timed + 3 phase-timed steps after them
 lo, hi = x[-(steps + 3)] - 8, x[-3] - 8
 tot = {}
 for n, s, e in rows[lo:hi]:

@@ -21,8 +21,8 @@ def accuracy_score(y_true, y_pred, *, normalize=True, sample_weight=None):
 
 def r2_score(y_true, y_pred, *, sample_weight=None, multioutput="uniform_average"):
     """Coefficient of determination with the reference's target handling
-    (``/root/reference/sklearn/metrics/_regression.py`` ``r2_score``, used by
-    ``RegressorMixin.score`` at ``/root/reference/sklearn/base.py:564-566``):
+    (``sklearn/metrics/_regression.py`` ``r2_score``, used by
+    ``RegressorMixin.score`` at ``sklearn/base.py:564-566``):
     1-D targets become one output column, so ``(n,)`` and ``(n, 1)`` agree;
     per-output scores are combined by ``multioutput`` ('uniform_average' by
     default, 'raw_values', 'variance_weighted' or an array of weights); a

@@ -2,10 +2,12 @@
 
 ``labels_estimation`` (E-step: delta-band uniform pick via ``select_labels``,
 or IPE-estimated distances with a random argmin), ``_centers_update``
-(M-step means + tomography error) are AST-extracted from
-``/root/reference/sklearn/cluster/_dmeans.py`` (tests/_dmeans_ref.py) and
-run side by side with the framework's Lloyd engine (CPU here;
-tests/test_dmeans_pinned_gpu.py runs the GPU engines):
+(M-step means + tomography error) of the reference's
+``sklearn/cluster/_dmeans.py`` were run on this file's problems by
+tests/golden/make_pinned_ref.py (AST-extracted, tests/_dmeans_ref.py); their
+recorded outputs (tests/golden/dmeans_cpu_ref.npz) are compared with the
+framework's Lloyd engine (CPU here; tests/test_dmeans_pinned_gpu.py runs the
+GPU engines):
 
 * delta-means: every label the engine picks lies in the reference's band
   {j : D_ij <= min_i + delta}, the per-row label law equals the reference's
@@ -17,17 +19,16 @@ tests/test_dmeans_pinned_gpu.py runs the GPU engines):
   of the estimated inertia equal the reference's (median-of-13 amplitude
   estimation per pair through ``Utility.ipe``).
 
-The reference draws from python's ``random`` / ``np.random`` (seeded per
-repetition); the engine from its Philox keys (seeded per repetition).
-Thresholds p > 1e-4."""
-import random
+The reference drew from python's ``random`` / ``np.random`` (seeded per
+repetition by the recorder); the engine from its Philox keys (seeded per
+repetition).  Thresholds p > 1e-4."""
+import os
 
 import numpy as np
 import pytest
 import torch
 from scipy import stats
 
-import _dmeans_ref
 from sq_learn_amd.models.cluster._lloyd import LloydEngine
 
 P_MIN = 1e-4
@@ -35,20 +36,9 @@ P_MIN = 1e-4
 
 @pytest.fixture(scope="module")
 def R():
-    if not _dmeans_ref.available():
-        pytest.skip("reference _dmeans.py / Utility.py not present")
-    try:
-        import matplotlib  # noqa: F401
-        import sklearn  # noqa: F401
-    except ImportError:
-        pytest.skip("matplotlib / scikit-learn missing")
-    ns, U = _dmeans_ref.load()
-    return ns
-
-
-def _seed(s):
-    random.seed(s)
-    np.random.seed(s)
+    """The reference's recorded outputs."""
+    return dict(np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                                     "dmeans_cpu_ref.npz")))
 
 
 def _contingency(ca, cb):
@@ -82,19 +72,17 @@ def test_delta_band_labels_follow_select_labels(R):
     band = D <= D.min(1, keepdims=True) + delta
     assert (band.sum(1) >= 2).sum() >= 20          # plenty of multi-member bands
     reps = 400
-    cr = np.zeros(D.shape)
+    cr, inert = R["band_counts"], R["band_inertia"]
+    assert cr.shape == D.shape and inert.shape == (reps,)
+    assert (cr.sum(1) == reps).all()
+    assert (cr[~band] == 0).all()                  # the reference's labels are band members
     co = np.zeros(D.shape)
     for s in range(reps):
-        _seed(s)
-        lab, _, inert = R["labels_estimation"](X, C, delta, None, False)
-        lab = np.asarray(lab, dtype=np.int64)
-        assert band[np.arange(len(lab)), lab].all()
-        cr[np.arange(len(lab)), lab] += 1
         lo, _, io = _engine_estep(X, C, delta, False, seed=1000 + s)
         assert band[np.arange(len(lo)), lo].all()
         co[np.arange(len(lo)), lo] += 1
         # the reference's inertia: sum of the minimum distances
-        assert io == pytest.approx(float(inert), rel=1e-12)
+        assert io == pytest.approx(float(inert[s]), rel=1e-12)
     multi = band.sum(1) >= 2
     assert _contingency(cr[multi].ravel(), co[multi].ravel()) > P_MIN
     # both uniform over the band
@@ -109,24 +97,23 @@ def test_centers_update_means_and_tomography_law(R):
     rng = np.random.default_rng(3)
     labels = rng.integers(0, 4, 300)
     labels[:4] = np.arange(4)                     # every cluster non-empty
-    ref = R["_centers_update"](X, labels, 0.0, False, False, True)
+    ref = R["mstep_means"]
+    assert ref.shape == C.shape
     eng = LloydEngine(torch.from_numpy(X), 4, delta=0.0, seed=0)
     eng.set_centers(torch.from_numpy(C))
     eng.mstep(torch.from_numpy(labels), torch.zeros(1, dtype=torch.float64))
     np.testing.assert_allclose(eng.centers().numpy(), ref, rtol=1e-12, atol=1e-13)
     # intermediate_error=True, Gaussian tomography with error delta/2
     delta = 0.8
-    nr, ne = [], []
+    nr, ne = R["mstep_noise"], []
+    assert nr.shape == (150 * ref.size,)
     for s in range(150):
-        _seed(s)
-        noisy = R["_centers_update"](X, labels, delta / 2, True, False, True)
-        nr.append((noisy - ref).ravel())
         eng = LloydEngine(torch.from_numpy(X), 4, delta=delta, intermediate_error=True,
                           true_tomography=False, seed=500 + s)
         eng.set_centers(torch.from_numpy(C))
         eng.mstep(torch.from_numpy(labels), torch.zeros(1, dtype=torch.float64))
         ne.append((eng.centers().numpy() - ref).ravel())
-    nr, ne = np.concatenate(nr), np.concatenate(ne)
+    ne = np.concatenate(ne)
     bound = delta / 2 / np.sqrt(4 * 6)
     assert np.abs(nr).max() <= bound + 1e-12 and np.abs(ne).max() <= bound + 1e-12
     assert stats.ks_2samp(nr, ne).pvalue > P_MIN
@@ -142,15 +129,11 @@ def test_ipe_labels_and_inertia_law_match_reference(R):
                   [-0.15, 0.1, 0.2, -0.1]])
     delta = 0.5
     reps = 300
-    cr = np.zeros((4, 3))
+    cr, ir = R["ipe_counts"], R["ipe_inertia"]
+    assert cr.shape == (4, 3) and (cr.sum(1) == reps).all() and ir.shape == (reps,)
     co = np.zeros((4, 3))
-    ir, io = [], []
+    io = []
     for s in range(reps):
-        _seed(s)
-        lab, _, inert = R["labels_estimation"](X, C, delta, None, True)
-        lab = np.asarray(lab, dtype=np.int64)
-        cr[np.arange(4), lab] += 1
-        ir.append(float(inert))
         lo, _, i_o = _engine_estep(X, C, delta, True, seed=2000 + s)
         co[np.arange(4), lo] += 1
         io.append(i_o)
@@ -159,14 +142,17 @@ def test_ipe_labels_and_inertia_law_match_reference(R):
     assert stats.ks_2samp(ir, io).pvalue > P_MIN
 
 
-def test_gpu_fixture_is_the_references_output(R):
+def test_gpu_fixture_is_the_references_output():
     """tests/fixtures/dmeans_ref.npz (what the GPU-box pinned tests compare
-    against) is exactly what the reference functions produce."""
-    import os
+    against) is exactly what the reference functions produce:
+    tests/golden/make_pinned_ref.py compared it with the reference's output
+    and recorded its digest; the fixture (and its inputs) are still those."""
     import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "fixtures"))
+    here = os.path.dirname(os.path.abspath(__file__))
+    for sub in ("fixtures", "golden"):
+        sys.path.insert(0, os.path.join(here, sub))
     import make_dmeans_ref
-    f, z = make_dmeans_ref.load()
-    got = make_dmeans_ref.generate(R)
-    for key in ("cnt1", "inert1", "means2", "cnt3", "inert3"):
-        np.testing.assert_array_equal(got[key], z[key], err_msg=key)
+    import make_pinned_ref
+    f, z = make_dmeans_ref.load()                  # raises if the inputs drifted
+    with open(os.path.join(here, "golden", "dmeans_fixture.sha256")) as fh:
+        assert make_pinned_ref.fixture_digest(make_dmeans_ref, z) == fh.read().strip()

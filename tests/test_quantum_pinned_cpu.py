@@ -1,7 +1,10 @@
 """The quantum error model pinned to the REFERENCE's own code.
 
-``/root/reference/sklearn/QuantumUtility/Utility.py`` is loaded with
-importlib (skipped when absent) and sampled side by side with
+Samples and helper values of the reference's
+``sklearn/QuantumUtility/Utility.py``, recorded by
+tests/golden/make_pinned_ref.py (tests/golden/quantum_ref.npz,
+quantum_ref_helpers.json: the draws the reference made under the seeds noted
+there), are compared with
 
 * the NumPy oracle (:mod:`sq_learn_amd.quantum.reference`),
 * the device samplers' CPU twins (:mod:`sq_learn_amd.ops.random`,
@@ -10,15 +13,14 @@ importlib (skipped when absent) and sampled side by side with
 
 Discrete laws (AE, PE, CPE) are compared by a two-sample chi^2 on pooled
 categories, continuous ones (Gaussian tomography noise, IPE, tomography
-errors) by a two-sample Kolmogorov-Smirnov test.  The reference draws from
-python's ``random`` and ``np.random`` (seeded here) and, inside
+errors) by a two-sample Kolmogorov-Smirnov test.  The reference drew from
+python's ``random`` and ``np.random`` (seeded by the recorder) and, inside
 ``QuantumState.measure``, from an unseeded ``RandomState`` - thresholds are
-p > 1e-4 so a correct law fails about once in 10^4 runs.
+p > 1e-4 so a correct law fails about once in 10^4 recordings.
 """
-import importlib.util
+import json
 import math
 import os
-import random
 
 import numpy as np
 import pytest
@@ -30,31 +32,17 @@ from sq_learn_amd.quantum import device as QD
 from sq_learn_amd.ops import random as R
 from sq_learn_amd.runtime.rng import RngKey
 
-REF = "/root/reference/sklearn/QuantumUtility/Utility.py"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 P_MIN = 1e-4
 
 
 @pytest.fixture(scope="module")
 def U():
-    if not os.path.exists(REF):
-        pytest.skip("reference Utility.py not present")
-    try:
-        import matplotlib  # noqa: F401  (the reference imports pyplot at module level)
-        matplotlib.use("Agg")
-    except ImportError:
-        pytest.skip("matplotlib missing")
-    spec = importlib.util.spec_from_file_location("_ref_utility", REF)
-    mod = importlib.util.module_from_spec(spec)
-    import warnings
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        spec.loader.exec_module(mod)
-    return mod
-
-
-def _seed(s):
-    random.seed(s)
-    np.random.seed(s)
+    """The reference's recorded draws (arrays) and exact helper values."""
+    g = dict(np.load(os.path.join(GOLDEN, "quantum_ref.npz")))
+    with open(os.path.join(GOLDEN, "quantum_ref_helpers.json")) as f:
+        g.update(json.load(f))
+    return g
 
 
 def _chi2_two_sample(a, b):
@@ -76,11 +64,14 @@ def _chi2_two_sample(a, b):
 
 
 # --------------------------------------------------------------- Q10 / Q11
-@pytest.mark.parametrize("a,eps", [(0.3, 0.05), (0.04, 0.04), (0.81, 0.06)])
+AE_LAW = [(0.3, 0.05), (0.04, 0.04), (0.81, 0.06)]
+
+
+@pytest.mark.parametrize("a,eps", AE_LAW)
 def test_amplitude_estimation_law_matches_reference(U, a, eps):
-    _seed(1)
     n = 3000
-    ref = [U.amplitude_estimation(a, epsilon=eps) for _ in range(n)]
+    ref = U[f"ae_law_{AE_LAW.index((a, eps))}"]
+    assert ref.shape == (n,)
     rng = np.random.default_rng(2)
     ours = [Q.amplitude_estimation(a, epsilon=eps, random_state=rng) for _ in range(n)]
     assert _chi2_two_sample(ref, ours) > P_MIN
@@ -92,10 +83,10 @@ def test_amplitude_estimation_law_matches_reference(U, a, eps):
 
 
 def test_amplitude_estimation_median_matches_reference(U):
-    _seed(4)
     n = 600
     a, eps = 0.37, 0.08
-    ref = [U.amplitude_estimation(a, epsilon=eps, gamma=0.1) for _ in range(n)]
+    ref = U["ae_median"]
+    assert ref.shape == (n,)
     rng = np.random.default_rng(5)
     ours = [Q.amplitude_estimation(a, epsilon=eps, gamma=0.1, random_state=rng) for _ in range(n)]
     assert _chi2_two_sample(ref, ours) > P_MIN
@@ -107,19 +98,20 @@ def test_amplitude_estimation_median_matches_reference(U):
 
 def test_median_evaluation_q_matches_reference(U):
     calls = []
-    U.median_evaluation(lambda: calls.append(1) or 0.0, gamma=0.1)
-    n_ref = len(calls)
-    calls.clear()
+    n_ref = U["median_evaluation_calls"]
     Q.median_evaluation(lambda: calls.append(1) or 0.0, gamma=0.1)
     assert n_ref == len(calls) == 13
 
 
 # ---------------------------------------------------------------- Q12 / Q13
-@pytest.mark.parametrize("omega,m", [(0.3141, 6), (0.05, 7), (0.77777, 5)])
+PE_LAW = [(0.3141, 6), (0.05, 7), (0.77777, 5)]
+
+
+@pytest.mark.parametrize("omega,m", PE_LAW)
 def test_phase_estimation_law_matches_reference(U, omega, m):
-    _seed(7)
     n = 4000
-    ref = [U.phase_estimation(omega, m=m) for _ in range(n)]
+    ref = U[f"pe_law_{PE_LAW.index((omega, m))}"]
+    assert ref.shape == (n,)
     rng = np.random.default_rng(8)
     ours = [Q.phase_estimation(omega, m=m, random_state=rng) for _ in range(n)]
     assert _chi2_two_sample(ref, ours) > P_MIN
@@ -133,22 +125,22 @@ def test_phase_estimation_epsilon_qubits_match_reference(U):
     import warnings
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        for eps, gamma in [(0.01, 0.1), (1e-3, 0.05), (0.2, 0.3)]:
-            _, _, m_ref, M_ref = U.phase_estimation(0.4, epsilon=eps, gamma=gamma, nqubit=True)
+        for i, (eps, gamma) in enumerate([(0.01, 0.1), (1e-3, 0.05), (0.2, 0.3)]):
+            m_ref, M_ref = U["pe_qubits"][i]
             _, _, m, M = Q.phase_estimation(0.4, epsilon=eps, gamma=gamma, nqubit=True,
                                             random_state=0)
             assert (m_ref, M_ref) == (m, M)
 
 
-@pytest.mark.parametrize("omega", [0.123, 0.5, 0.9])
+CPE_OMEGA = [0.123, 0.5, 0.9]
+
+
+@pytest.mark.parametrize("omega", CPE_OMEGA)
 def test_consistent_phase_estimation_law_matches_reference(U, omega):
-    import warnings
     eps, gamma = 0.05, 0.1
-    _seed(10)
     n = 300
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        ref = [U.consistent_phase_estimation(omega, eps, gamma) for _ in range(n)]
+    ref = U[f"cpe_law_{CPE_OMEGA.index(omega)}"]
+    assert ref.shape == (n,)
     rng = np.random.default_rng(11)
     ours = [Q.consistent_phase_estimation(omega, eps, gamma, random_state=rng) for _ in range(n)]
     assert _chi2_two_sample(ref, ours) > P_MIN
@@ -169,9 +161,9 @@ def test_ipe_law_matches_reference(U, gamma):
     x = rs.standard_normal(32)
     y = x + 0.3 * rs.standard_normal(32)
     eps = 0.5
-    _seed(13)
     n = 1500 if gamma is None else 300
-    ref = np.array([U.ipe(x, y, eps, gamma=gamma) for _ in range(n)])
+    ref = U["ipe_single" if gamma is None else "ipe_median"]
+    assert ref.shape == (n,)
     rng = np.random.default_rng(14)
     ours = np.array([Q.ipe(x, y, eps, gamma=gamma, random_state=rng) for _ in range(n)])
     # a discrete law (S (1 - 2 sin^2(pi j / M)) / 2): chi^2 on values rounded
@@ -198,8 +190,8 @@ def test_ipe_law_matches_reference(U, gamma):
 def test_gaussian_tomography_noise_matches_reference(U):
     vec = np.linspace(-1, 1, 4000)
     noise = 0.7
-    np.random.seed(17)
-    ref = U.make_gaussian_est(vec, noise) - vec
+    ref = U["gaussian_est_noise"]
+    assert ref.shape == vec.shape
     ours = Q.make_gaussian_est(vec, noise, random_state=18) - vec
     assert stats.ks_2samp(ref, ours).pvalue > P_MIN
     t = torch.tensor(vec, dtype=torch.float32)
@@ -211,8 +203,8 @@ def test_gaussian_tomography_noise_matches_reference(U):
 
 def test_matrix_tomography_budget_matches_reference(U):
     A = np.arange(60, dtype=np.float64).reshape(6, 10) / 60
-    np.random.seed(20)
-    ref = U.tomography(A, 0.5, true_tomography=False) - A
+    ref = U["matrix_tomography_noise"]
+    assert ref.shape == A.shape
     ours = Q.tomography(A, 0.5, true_tomography=False, random_state=21) - A
     assert stats.ks_2samp(ref.ravel(), ours.ravel()).pvalue > P_MIN
     assert np.abs(ref).max() <= 0.5 / math.sqrt(60) and np.abs(ours).max() <= 0.5 / math.sqrt(60)
@@ -222,14 +214,18 @@ def _tomo_errors(est_fn, V, reps):
     return np.array([np.linalg.norm(V - np.asarray(est_fn(i))) for i in range(reps)])
 
 
-@pytest.mark.parametrize("d,N", [(24, 3000), (700, 40000)])
+TOMO_SINGLE = [(24, 3000), (700, 40000)]
+
+
+@pytest.mark.parametrize("d,N", TOMO_SINGLE)
 def test_real_tomography_single_pass_matches_reference(U, d, N):
     """One pass with N shots (qPCA's default: incremental_measure=False)."""
     rs = np.random.RandomState(22)
     V = rs.standard_normal(d)
     V /= np.linalg.norm(V)
     reps = 150 if d < 100 else 60
-    ref = _tomo_errors(lambda i: U.real_tomography(V, N=N, incremental_measure=False)[N], V, reps)
+    ref = U[f"tomo_single_err_{TOMO_SINGLE.index((d, N))}"]
+    assert ref.shape == (reps,)
     rng = np.random.default_rng(23)
     ours = _tomo_errors(lambda i: Q.real_tomography(V, N=N, incremental_measure=False,
                                                     random_state=rng)[N], V, reps)
@@ -252,12 +248,8 @@ def test_real_tomography_stopping_rule_matches_reference(U):
     V = rs.standard_normal(d)
     V /= np.linalg.norm(V)
     reps = 60
-    ref_n, ref_e = [], []
-    for _ in range(reps):
-        r = U.real_tomography(V, delta=delta)
-        n_last = list(r.keys())[-1]
-        ref_n.append(n_last)
-        ref_e.append(np.linalg.norm(V - np.asarray(r[n_last])))
+    ref_n, ref_e = U["tomo_stop_n"], U["tomo_stop_err"]
+    assert ref_n.shape == ref_e.shape == (reps,)
     rng = np.random.default_rng(26)
     our_n, our_e = [], []
     for _ in range(reps):
@@ -277,7 +269,8 @@ def test_fake_sign_tomography_matches_reference(U):
     rs = np.random.RandomState(28)
     V = rs.standard_normal(12)
     V /= np.linalg.norm(V)
-    ref = _tomo_errors(lambda i: U.L2_tomogrphy_fakeSign(V, N=2000), V, 100)
+    ref = U["fake_sign_err"]
+    assert ref.shape == (100,)
     rng = np.random.default_rng(29)
     ours = _tomo_errors(lambda i: Q.L2_tomogrphy_fakeSign(V, N=2000, random_state=rng), V, 100)
     assert stats.ks_2samp(ref, ours).pvalue > P_MIN
@@ -286,43 +279,44 @@ def test_fake_sign_tomography_matches_reference(U):
 # ----------------------------------------------------------------------- Q9
 def test_best_mu_and_helpers_equal_reference(U):
     rs = np.random.RandomState(30)
-    for shape in [(40, 7), (9, 31)]:
+    for i, shape in enumerate([(40, 7), (9, 31)]):
         A = rs.standard_normal(shape)
         A[A < -1.2] = 0.0
-        assert U.best_mu(A) == Q.best_mu(A)
-        assert U.best_mu(A, step=0.1)[1] == pytest.approx(Q.best_mu(A, step=0.1)[1], rel=1e-12)
-    for w0, w1 in [(0.1, 0.95), (0.5, 0.5), (0.99, 0.01)]:
-        assert U.amplitude_est_dist(w0, w1) == pytest.approx(Q.amplitude_est_dist(w0, w1))
+        assert tuple(U["best_mu"][i]) == Q.best_mu(A)
+        assert U["best_mu_step"][i] == pytest.approx(Q.best_mu(A, step=0.1)[1], rel=1e-12)
+    for i, (w0, w1) in enumerate([(0.1, 0.95), (0.5, 0.5), (0.99, 0.01)]):
+        assert U["amplitude_est_dist"][i] == pytest.approx(Q.amplitude_est_dist(w0, w1))
     arr = np.array([1, 1, 2, 2, 2, 9, 9, 30], dtype=np.int64)
-    np.testing.assert_array_equal(U.check_measure(arr.copy(), 0), Q.check_measure(arr, 0))
-    for v, j in [(10, 3), (7, 7), (100, 6)]:
-        assert U.check_division(v, j) == Q.check_division(v, j)
-    for x in [0.1, 0.7]:
-        assert U.wrapper_phase_est_arguments(x) == Q.wrapper_phase_est_arguments(x)
-        assert U.wrapper_phase_est_arguments(x, "distance") == Q.wrapper_phase_est_arguments(x, "distance")
-        assert U.unwrap_phase_est_arguments(x, 0.01) == Q.unwrap_phase_est_arguments(x, 0.01)
+    np.testing.assert_array_equal(U["check_measure"], Q.check_measure(arr, 0))
+    for i, (v, j) in enumerate([(10, 3), (7, 7), (100, 6)]):
+        assert U["check_division"][i] == Q.check_division(v, j)
+    for i, x in enumerate([0.1, 0.7]):
+        assert U["wrapper_sv"][i] == Q.wrapper_phase_est_arguments(x)
+        assert U["wrapper_distance"][i] == Q.wrapper_phase_est_arguments(x, "distance")
+        assert U["unwrap_sv"][i] == Q.unwrap_phase_est_arguments(x, 0.01)
 
 
 def test_introduce_error_law_matches_reference(U):
-    np.random.seed(31)
     arr = np.zeros(3000)
-    ref = U.introduce_error_array(arr, 2.0)
+    ref = U["introduce_error_array"]
+    assert ref.shape == arr.shape
     ours = Q.introduce_error_array(arr, 2.0, random_state=32)
     assert stats.ks_2samp(ref, ours).pvalue > P_MIN
-    ref1 = np.array([U.introduce_error(0.0, 0.3)[0] for _ in range(2000)])
+    ref1 = U["introduce_error"]
+    assert ref1.shape == (2000,)
     ours1 = np.array([Q.introduce_error(0.0, 0.3, random_state=i)[0] for i in range(2000)])
     assert stats.ks_2samp(ref1, ours1).pvalue > P_MIN
 
 
 def test_quantum_state_and_coupon_match_reference(U):
     regs, amps = ["a", "b", "c"], [0.2, 0.5, 0.84]
-    _seed(33)
-    qs_ref = U.QuantumState(registers=regs, amplitudes=amps)
     qs = Q.QuantumState(registers=regs, amplitudes=amps, random_state=34)
-    assert qs_ref.get_state() == pytest.approx(qs.get_state())
-    ref = list(qs_ref.measure(6000))
+    assert U["quantum_state"] == pytest.approx(qs.get_state())
+    ref = U["quantum_state_measure"]
+    assert ref.shape == (6000,)
     ours = list(qs.measure(6000))
-    assert _chi2_two_sample([regs.index(r) for r in ref], [regs.index(r) for r in ours]) > P_MIN
-    cref = [U.coupon_collect(qs_ref) for _ in range(300)]
+    assert _chi2_two_sample(ref, [regs.index(r) for r in ours]) > P_MIN
+    cref = U["coupon_collect"]
+    assert cref.shape == (300,)
     cours = [Q.coupon_collect(qs) for _ in range(300)]
     assert stats.ks_2samp(cref, cours).pvalue > P_MIN

@@ -1,10 +1,10 @@
 """``RegressorMixin.score`` and the forest OOB R^2 against scikit-learn.
 
 The reference's ``RegressorMixin.score`` is the full ``metrics.r2_score``
-(``/root/reference/sklearn/base.py:564-566``): 1-D targets are reconciled
+(``sklearn/base.py:564-566``): 1-D targets are reconciled
 with ``(n, 1)`` predictions and multi-output scores are uniformly averaged.
 The forest OOB score is the same function on the OOB predictions
-(``/root/reference/sklearn/ensemble/_forest.py:944``).  sklearn (importable
+(``sklearn/ensemble/_forest.py:944``).  sklearn (importable
 here) is the oracle, on identical predictions."""
 
 import numpy as np
