@@ -42,33 +42,11 @@
 // epilogue of tile t runs in the MFMA shadow of tile t+1.
 #include "common.h"
 #include "band.h"
-#include <utility>
+#include "f16_tile.h"
 
 namespace sq {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kTileN = 64;          // centroids per LDS tile
 constexpr int kMaxCand = 16;        // candidates per multi row (fp64 re-check list)
-
-SQ_DEV float vmin(float a, float b) {
-  float r;
-  asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-// (bits(a) & m) | q in ONE VALU op (v_and_or_b32; the compiler emits an and
-// plus an or3 that it pairs across values)
-SQ_DEV float and_or(float a, uint32_t m, uint32_t q) {
-  float r;
-  asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(m), "v"(q));   // one SGPR per VOP3 on gfx9
-  return r;
-}
-SQ_DEV float vmed3(float a, float b, float c) {
-  float r;
-  asm("v_med3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
-}
 
 // TOP = 2: per lane the two smallest values are band members, a 3rd in the
 // band -> overflow.  TOP = 3 (the overflow rows of a TOP = 2 pass, in list
@@ -116,9 +94,9 @@ __global__ void __launch_bounds__(256, 1) estep_f32_kernel(
   auto map_row = [&](long long r) -> long long { return rlist ? rlist[r] : r; };
   constexpr int NW = 4;
   constexpr int DX = KSD * 16;                 // fp32 row length (padded features)
-  constexpr int HI_BYTES = (KSD + 1) * 2048;   // data chunks + norm chunk pair
-  constexpr int TILE_BYTES = HI_BYTES + KSD * 2048;
-  constexpr int PIECES = TILE_BYTES / 1024;
+  constexpr int HI_BYTES = f16op::hi_bytes(KSD);   // data chunks + norm chunk pair
+  constexpr int TILE_BYTES = f16op::tile_bytes(KSD);
+  constexpr int PIECES = TILE_BYTES / f16op::kChunkBytes;
   constexpr int ROWS = NW * 32;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   auto buf = [&](int g) -> unsigned char* { return smem + (g & 1) * TILE_BYTES; };
@@ -179,8 +157,7 @@ __global__ void __launch_bounds__(256, 1) estep_f32_kernel(
   float m1[16], m2[16], m3[16], m4[TOP == 3 ? 16 : 1];
   int i1[16], i2[16], i3[TOP == 3 ? 16 : 1];
 
-  const int lane_off = (half * 64 + r32) * 16;
-  auto ldb = [&](const unsigned char* p) -> f16x8 { return *reinterpret_cast<const f16x8*>(p); };
+  const int lane_off = f16op::lane_off(half, r32);
 
   auto tile_step = [&](const unsigned char* cur, f32x16& n0, f32x16& n1, bool do_mfma,
                        const f32x16& o0, const f32x16& o1, int t_prev, bool do_epi) {
@@ -359,7 +336,7 @@ __global__ void __launch_bounds__(256, 1) estep_f32_kernel(
     merge(q1, q2, qi, __shfl_xor(R1[0], 1, 64), __shfl_xor(R2[0], 1, 64), __shfl_xor(RI[0], 1, 64));
 
     const int irow = r32 >> 1;
-    const int rloc = (irow & 3) + 8 * (irow >> 2) + 4 * half;
+    const int rloc = acc_row(irow, half);
     const long long grow_local = row0 + rloc;
     const bool owner = ((r32 & 1) == 0) && grow_local < n;
     const float thr = q1 + delta_s;
@@ -560,17 +537,8 @@ struct __align__(16) GapRec {
   float g[kGapCand];
   unsigned ids[2];
 };
-#ifndef SQ_X64_NW
-#define SQ_X64_NW 4
-#endif
-constexpr int kX64Waves = SQ_X64_NW;   // waves per workgroup (8: 2 per SIMD, spills)
-#ifndef SQ_X64_RING
-#define SQ_X64_RING 3
-#endif
-#ifndef SQ_X64_PIN
-#define SQ_X64_PIN 1
-#endif
-constexpr int kX64Ring = SQ_X64_RING;  // centroid-tile LDS slots (3: 2 tiles in flight)
+
+constexpr int kX64Waves = 4;   // waves per workgroup (8: 2 per SIMD, spills)
 
 // Diagnostic build only (-DSQ_X64_STAMP=1, a variant library): per-wave
 // s_memtime sums of the kernel's phases go to a buffer of their own (never an
@@ -588,43 +556,22 @@ __device__ unsigned long long g_x64_stamps[kStampWaves * kStampN];
 #define SQ_STAMP_NOW() __builtin_amdgcn_s_memtime()
 #endif
 
-// Tile geometry of the certified filter: a 64-centroid tile is KT = KSD + 1
-// k-steps (d_pad / 16 data steps + the norm step) of 2 KiB each.  Up to
-// d_pad = 256 a whole tile is one LDS ring slot; above, the tile is staged in
-// NS sub-tiles of at most 24 k-steps (48 KiB) so the 3-slot ring stays within
-// the 160 KiB LDS at every d_pad <= 1024, and the accumulation of a tile spans
-// NS slots (one counted-vmcnt barrier each).  The A operand (the wave's 32
-// rows, d_pad / 4 fp16x2 registers) stays resident for the whole sweep.
+// Tile geometry of the certified filter: TileRing (f16_tile.h).  A tile is
+// KT = KSD + 1 k-steps (d_pad / 16 data steps + the norm step); above
+// d_pad = 256 its accumulation spans NS ring slots (one counted-vmcnt barrier
+// each).  The A operand (the wave's 32 rows, d_pad / 4 fp16x2 registers)
+// stays resident for the whole sweep.
 template <int KSD>
-struct X64Geom {
-  static constexpr int KT = KSD + 1;
-  static constexpr int NS = (KT + 23) / 24;
-  static constexpr int SK = (KT + NS - 1) / NS;    // k-steps per slot
-  static constexpr int SLOT = SK * 2048;           // bytes per LDS slot
-};
+using X64Ring = TileRing<KSD, kX64Waves>;
 
 // Row sets of 32 per wave: 2 (64 rows share each staged B fragment - half
 // the L2 -> LDS staging per row, which bounds the d <= 256 sweep) while the
 // A fragments fit the registers; 1 above d_pad = 256.
-#ifndef SQ_X64_RS
-#define SQ_X64_RS 2
-#endif
-#ifndef SQ_X64_PFD
-#define SQ_X64_PFD 2   // B-fragment read distance of the row-set sweep (k-steps)
-#endif
 template <int KSD>
 struct X64RowSets {
-  static constexpr int value = KSD <= 16 ? SQ_X64_RS : 1;
+  static constexpr int value = KSD <= 16 ? 2 : 1;
 };
-
-template <typename F, int... I>
-SQ_DEV void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, typename F>
-SQ_DEV void static_for(F&& f) {
-  static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
+constexpr int kX64Pfd = 2;   // B-fragment read distance of the row-set sweep (k-steps)
 
 template <int KSD, int RS>
 __global__ void __launch_bounds__(kX64Waves * 64) estep_x64_kernel(
@@ -638,16 +585,12 @@ __global__ void __launch_bounds__(kX64Waves * 64) estep_x64_kernel(
     int* __restrict__ mflag) {
   constexpr int NW = kX64Waves;
   constexpr int DX = KSD * 16;
-  using GEO = X64Geom<KSD>;
-  constexpr int KT = GEO::KT, NS = GEO::NS, SK = GEO::SK, SLOT = GEO::SLOT;
-  constexpr int TILE_STRIDE = (2 * KSD + 1) * 2048;
-  constexpr int PIECES = SLOT / 1024;           // 1 KiB LDS-DMA pieces per slot
+  using Ring = X64Ring<KSD>;
+  constexpr int KT = Ring::KT, NS = Ring::NS, SK = Ring::SK, RING = Ring::RING;
   constexpr int ROWS = NW * 32 * RS;              // RS sets of 32 rows per wave
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int RING = kX64Ring;                // LDS slots
-  constexpr int PPW = (PIECES + NW - 1) / NW;   // glds per wave per stage (uniform: counted vmcnt)
-  auto buf = [&](int g) -> unsigned char* { return smem + (g % RING) * SLOT; };
-  int* cand_all = reinterpret_cast<int*>(smem + RING * SLOT);        // [NW][RS][32][kMaxCand]
+  auto buf = [&](int g) -> unsigned char* { return Ring::buf(smem, g); };
+  int* cand_all = reinterpret_cast<int*>(smem + Ring::BYTES);         // [NW][RS][32][kMaxCand]
   int* cnt_all = cand_all + NW * RS * 32 * kMaxCand;                  // [NW][RS][32], then [NW][64] dump slots
 
   const int tid = threadIdx.x;
@@ -673,54 +616,31 @@ __global__ void __launch_bounds__(kX64Waves * 64) estep_x64_kernel(
   const float pack_rel = ldexpf(1.0f, qbits - 23) + 0x1p-15f;
   const float sub_rel = 0x1p-21f * sqrtf((float)DX);
 
-  // unit U = sub-tile U % NS of tile (U / NS) % n_tiles (the sequence runs on
-  // across row blocks: the next block's first tiles are staged during the
-  // current block's last ones)
-  auto stage = [&](int U) {
-    const int t = (NS == 1 ? U : U / NS) % n_tiles;
-    const int sub = NS == 1 ? 0 : U % NS;
-    const int npc = 2 * min(SK, KT - sub * SK);   // valid pieces of this sub-tile
-    const unsigned char* tile = reinterpret_cast<const unsigned char*>(C) + (size_t)t * TILE_STRIDE +
-                                (size_t)sub * SLOT;
-    unsigned char* dst = buf(U);
-#pragma unroll
-    for (int i = 0; i < PPW; ++i) {
-      // every wave issues PPW loads (the surplus repeat the last piece: same
-      // bytes to the same LDS slot) so one counted vmcnt fits all waves
-      const int p = wave + NW * i < npc ? wave + NW * i : npc - 1;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)(tile + p * 1024 + lane * 16),
-          (__attribute__((address_space(3))) void*)(dst + p * 1024), 16, 0, 0);
-    }
-  };
+  // the unit sequence runs on across row blocks: the next block's first
+  // tiles are staged during the current block's last ones
+  auto stage = [&](int U) { Ring::stage(C, smem, U, n_tiles); };
 
   // the wave's RS sets of 32 rows share every B fragment (register blocking:
   // the staged centroid tiles are read once per 32 RS rows)
   f16x8 ah[RS][KSD];
   auto load_a = [&](long long b) {
-#pragma unroll
-    for (int st = 0; st < RS; ++st) {
-      const long long r = row_at(b * ROWS + (wave * RS + st) * 32 + r32);
-      const _Float16* xr = Xh + (size_t)r * DX + half * 8;
-#pragma unroll
-      for (int ks = 0; ks < KSD; ++ks) ah[st][ks] = *reinterpret_cast<const f16x8*>(xr + ks * 16);
-    }
+    sq::load_a(ah, half, [&](int st) {
+      return Xh + (size_t)row_at(b * ROWS + (wave * RS + st) * 32 + r32) * DX;
+    });
   };
-  f16x8 aug = (f16x8)0;
-  if (half == 0) { aug[0] = aug[1] = aug[2] = (_Float16)1.0f; }
+  const f16x8 aug = aug_frag(half);
   // |x|^2 of the row whose reduced minimum this lane ends with (rl_own of
   // each row set), loaded with the block's A operand so the epilogue does not
   // wait on a dependent global load
-  const int rl_lane = ((r32 >> 1) & 3) + 8 * ((r32 >> 1) >> 2) + 4 * half;
+  const int rl_own = acc_row(r32 >> 1, half);
   float xn_cur[RS], xn_nxt[RS];
   auto load_xn = [&](long long b, float (&dst)[RS]) {
 #pragma unroll
-    for (int st = 0; st < RS; ++st) dst[st] = xn[row_at(b * ROWS + (wave * RS + st) * 32 + rl_lane)];
+    for (int st = 0; st < RS; ++st) dst[st] = xn[row_at(b * ROWS + (wave * RS + st) * 32 + rl_own)];
   };
 
   float m1[RS][16], m2[RS][16], m3[RS][16];
-  const int lane_off = (half * 64 + r32) * 16;
-  auto ldb = [&](const unsigned char* p) -> f16x8 { return *reinterpret_cast<const f16x8*>(p); };
+  const int lane_off = f16op::lane_off(half, r32);
   auto ins = [&](int st, int i, float v, uint32_t q) {
     const float p = and_or(v, keep, q);   // (v & keep) | q: the tile index in the low bits
     const float a1 = m1[st][i], a2 = m2[st][i];
@@ -739,14 +659,14 @@ __global__ void __launch_bounds__(kX64Waves * 64) estep_x64_kernel(
     const uint32_t q0 = (uint32_t)(t_prev * 2), q1 = q0 + 1u;
     const unsigned char* hb = cur + lane_off;
     f16x8 b0[2], b1[2];
-    b0[0] = ldb(hb);
-    b1[0] = ldb(hb + 512);
+    b0[0] = ldb(hb + f16op::frag_off(0, 0));
+    b1[0] = ldb(hb + f16op::frag_off(1, 0));
 #pragma unroll
     for (int ks = K0; ks < K1; ++ks) {
       const int c = (ks - K0) & 1, nx = c ^ 1;
       if (ks + 1 < K1) {
-        b0[nx] = ldb(hb + (ks + 1 - K0) * 2048);
-        b1[nx] = ldb(hb + (ks + 1 - K0) * 2048 + 512);
+        b0[nx] = ldb(hb + f16op::frag_off(0, ks + 1 - K0));
+        b1[nx] = ldb(hb + f16op::frag_off(1, ks + 1 - K0));
       }
 #pragma unroll
       for (int st = 0; st < RS; ++st) {
@@ -762,9 +682,7 @@ __global__ void __launch_bounds__(kX64Waves * 64) estep_x64_kernel(
           ins(e / 16, e % 16, o[e / 16][1][e % 16], q1);
         }
       }
-#if SQ_X64_PIN
       __builtin_amdgcn_sched_barrier(0);
-#endif
     }
   };
   auto epi_all = [&](const Acc& o, int t_prev) {
@@ -777,11 +695,6 @@ __global__ void __launch_bounds__(kX64Waves * 64) estep_x64_kernel(
         ins(st, i, o[st][1][i], q1);
       }
   };
-  // RING == 2: the tile staged in this step must land before the barrier
-  // (vmcnt(0)).  RING == 3: staging runs two tiles ahead and the barrier
-  // only retires the tile staged one step earlier - vmcnt(PPW) leaves this
-  // step's glds in flight across the raw s_barrier (no __syncthreads: its
-  // fence would drain them).
 #if SQ_X64_STAMP
   unsigned long long st_sync = 0, st_sync0 = 0, st_post = 0, st_sweep = 0, st_blocks = 0;
   unsigned long long st_stage = 0, st_cand = 0, st_aload = 0, st_rmin = 0, st_cl = 0, st_ub = 0;
@@ -792,12 +705,7 @@ __global__ void __launch_bounds__(kX64Waves * 64) estep_x64_kernel(
 #if SQ_X64_STAMP
     const unsigned long long sa = SQ_STAMP_NOW();
 #endif
-    if constexpr (RING == 2) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW) : "memory");
-    }
-    __builtin_amdgcn_s_barrier();
+    Ring::sync();
 #if SQ_X64_STAMP
     const unsigned long long sw = SQ_STAMP_NOW() - sa;
     st_sync += sw;
@@ -823,7 +731,7 @@ __global__ void __launch_bounds__(kX64Waves * 64) estep_x64_kernel(
   };
 
   stage(0);
-  if constexpr (RING == 3) stage(1);
+  stage(1);
   load_a(blk);
   load_xn(blk, xn_cur);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -862,46 +770,10 @@ __global__ void __launch_bounds__(kX64Waves * 64) estep_x64_kernel(
       // during the next half's MFMAs - two RS x 16-register accumulator sets
       // live instead of four
       f32x16 cA[RS], cB[RS];
-      // B fragments stream through a ring of PFD + 1 registers, PFD k-steps
-      // ahead of their MFMAs (one k-step of cover - a single MFMA pair - left
-      // the ds_read_b128 latency exposed at every k-step); the two column
-      // halves of a tile are one stream of 2 KT fragments, so the second
-      // half's first reads are in flight during the first half's last MFMAs
-      constexpr int PFD = SQ_X64_PFD;
-      constexpr int NB = PFD + 1;
-      f16x8 bq[NB];
-      auto frag = [&](const unsigned char* cur, int g) -> f16x8 {
-        return ldb(cur + lane_off + (g / KT) * 512 + (g % KT) * 2048);
-      };
-      auto pass = [&](auto H_, const unsigned char* cur, f32x16 (&acc)[RS],
-                      const f32x16 (&o)[RS], uint32_t qo, bool do_epi) {
-        constexpr int h = decltype(H_)::value;
-#pragma unroll
-        for (int st = 0; st < RS; ++st) acc[st] = (f32x16){0};
-#pragma unroll
-        for (int ks = 0; ks < KT; ++ks) {
-          const int g = h * KT + ks;
-          if (g + PFD < 2 * KT) bq[(g + PFD) % NB] = frag(cur, g + PFD);
-#pragma unroll
-          for (int st = 0; st < RS; ++st)
-            acc[st] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ks < KSD ? ah[st][ks] : aug,
-                                                             bq[g % NB], acc[st], 0, 0, 0);
-          if (do_epi) {
-#pragma unroll
-            for (int e = (ks * 16 * RS) / KT; e < ((ks + 1) * 16 * RS) / KT; ++e)
-              ins(e / 16, e % 16, o[e / 16][e % 16], qo);
-          }
-#if SQ_X64_PIN
-          __builtin_amdgcn_sched_barrier(0);
-#endif
-        }
-      };
-      auto drain = [&](const f32x16 (&o)[RS], uint32_t qo) {
-#pragma unroll
-        for (int st = 0; st < RS; ++st)
-#pragma unroll
-          for (int i = 0; i < 16; ++i) ins(st, i, o[st][i], qo);
-      };
+      // (one k-step of B-fragment cover - a single MFMA pair - left the
+      // ds_read_b128 latency exposed at every k-step)
+      constexpr int PFD = kX64Pfd;
+      f16x8 bq[PFD + 1];
       static_assert(NS == 1, "row sets need whole tiles per LDS slot");
 #if SQ_X64_STAMP
       const unsigned long long sw0 = SQ_STAMP_NOW();
@@ -918,10 +790,9 @@ __global__ void __launch_bounds__(kX64Waves * 64) estep_x64_kernel(
 #endif
         // half 0 of tile t (with the previous tile's half 1), then half 1
         // (with this tile's half 0); packed index q = 2 t + half
-#pragma unroll
-        for (int j = 0; j < PFD; ++j) bq[j] = frag(buf(U), j);
-        pass(std::integral_constant<int, 0>{}, buf(U), cA, cB, (uint32_t)(2 * t - 1), t > 0);
-        pass(std::integral_constant<int, 1>{}, buf(U), cB, cA, (uint32_t)(2 * t), true);
+        tile_prime<KT>(buf(U), lane_off, bq);
+        half_pass<0>(buf(U), lane_off, ah, aug, bq, cA, cB, (uint32_t)(2 * t - 1), t > 0, ins);
+        half_pass<1>(buf(U), lane_off, ah, aug, bq, cB, cA, (uint32_t)(2 * t), true, ins);
         sync_tile();
         ++U;
       }
@@ -933,7 +804,7 @@ __global__ void __launch_bounds__(kX64Waves * 64) estep_x64_kernel(
 #if SQ_X64_STAMP
       st_aload += SQ_STAMP_NOW() - sl0;
 #endif
-      drain(cB, (uint32_t)(2 * n_tiles - 1));
+      half_drain(cB, (uint32_t)(2 * n_tiles - 1), ins);
 #if SQ_X64_STAMP
       st_sweep += SQ_STAMP_NOW() - sw0;
 #endif
@@ -987,8 +858,6 @@ __global__ void __launch_bounds__(kX64Waves * 64) estep_x64_kernel(
 #pragma unroll
     for (int i = 0; i < 16; ++i) R[i] = ms1[i];
     const float rmin = row_min(R);
-    const int irow = r32 >> 1;
-    const int rl_own = (irow & 3) + 8 * (irow >> 2) + 4 * half;
     float xn_own = xn_cur[0];
 #pragma unroll
     for (int o = 1; o < RS; ++o) xn_own = st == o ? xn_cur[o] : xn_own;
@@ -1017,7 +886,7 @@ __global__ void __launch_bounds__(kX64Waves * 64) estep_x64_kernel(
     for (int i = 0; i < 16; ++i) {
       const float T = Tr[i];
       nc[i] = ms1[i] > T ? ms1[i] : (ms2[i] > T ? ms2[i] : ms3[i]);
-      const int rl = (i & 3) + 8 * (i >> 2) + 4 * half;
+      const int rl = acc_row(i, half);
       auto jof = [&](float p) -> int {
         const uint32_t q = __float_as_uint(p) & qmask;
         return (int)((q >> 1) * kTileN + (q & 1u) * 32u) + r32;
@@ -2326,11 +2195,9 @@ __global__ void __launch_bounds__(256) sum_f32_blocks_kernel(const float* __rest
 // one workgroup per padded centroid row.
 SQ_DEV void write_f16_operand_row(_Float16* op, int j, int k, const float* c, int d, int d_pad,
                                   float alpha, int tid, double* red) {
-  const int dch = d_pad / 8;
-  const int cpr = 2 * dch + 2;
-  _Float16* base = op + (size_t)(j >> 6) * cpr * 512 + (size_t)(j & 63) * 8;
-  auto hi_at = [&](int f) -> _Float16& { return base[(size_t)(f >> 3) * 512 + (f & 7)]; };
-  auto lo_at = [&](int f) -> _Float16& { return base[(size_t)(dch + 2 + (f >> 3)) * 512 + (f & 7)]; };
+  _Float16* base = op + f16op::row_base(d_pad, j);
+  auto hi_at = [&](int f) -> _Float16& { return base[f16op::hi_off(f)]; };
+  auto lo_at = [&](int f) -> _Float16& { return base[f16op::lo_off(d_pad, f)]; };
   double nn = 0.0;
   for (int f = tid; f < d_pad; f += 256) {
     _Float16 h = (_Float16)0.0f, l = (_Float16)0.0f;
@@ -2345,7 +2212,7 @@ SQ_DEV void write_f16_operand_row(_Float16* op, int j, int k, const float* c, in
     hi_at(f) = h;
     lo_at(f) = l;
   }
-  for (int f = d_pad + 3 + tid; f < d_pad + 16; f += 256) hi_at(f) = (_Float16)0.0f;
+  for (int f = d_pad + f16op::kNormElems + tid; f < d_pad + 16; f += 256) hi_at(f) = (_Float16)0.0f;
   nn = wave_sum(nn);
   if ((tid & 63) == 0) red[tid >> 6] = nn;
   __syncthreads();
@@ -2398,7 +2265,7 @@ static int launch_estep_f32(const void* X, const void* C, const void* xn, void* 
                             void* multi_count = nullptr, void* xflag = nullptr,
                             long long mcap = 0) {
   constexpr int NW = 4;
-  const size_t lds = 2 * (size_t)((2 * KSD + 1) * 2048);
+  const size_t lds = 2 * (size_t)f16op::tile_bytes(KSD);
   auto kern = estep_f32_kernel<KSD, TOP>;
   static bool attr = false;
   if (!attr) {
@@ -2406,13 +2273,7 @@ static int launch_estep_f32(const void* X, const void* C, const void* xn, void* 
     attr = true;
   }
   static int resident = 0;
-  if (resident == 0) {
-    int dev = 0, cus = 0, per_cu = 0;
-    hipGetDevice(&dev);
-    hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kern, NW * 64, lds);
-    resident = (cus > 0 ? cus : 256) * (per_cu > 0 ? per_cu : 1);
-  }
+  if (resident == 0) resident = resident_blocks((const void*)kern, NW * 64, lds);
   const long long nblk = (n + NW * 32 - 1) / (NW * 32);
   // list mode: the row count is on the device - every resident slot launches
   unsigned grid = (unsigned)(nblk < resident && !rlist ? nblk : resident);
@@ -2448,7 +2309,7 @@ static int launch_estep_x64(const void* Xh, const void* X, const void* C, const 
     constexpr int RS = decltype(RS_)::value;
     constexpr int NW = kX64Waves;
     const size_t lds =
-        kX64Ring * (size_t)X64Geom<KSD>::SLOT + (size_t)NW * RS * 32 * (kMaxCand + 1) * 4 +
+        (size_t)X64Ring<KSD>::BYTES + (size_t)NW * RS * 32 * (kMaxCand + 1) * 4 +
         (size_t)NW * 64 * 4;   // + per-lane dump slots
     auto kern = estep_x64_kernel<KSD, RS>;
     static bool attr = false;
@@ -2458,13 +2319,7 @@ static int launch_estep_x64(const void* Xh, const void* X, const void* C, const 
       attr = true;
     }
     static int resident = 0;
-    if (resident == 0) {
-      int dev = 0, cus = 0, per_cu = 0;
-      hipGetDevice(&dev);
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kern, NW * 64, lds);
-      resident = (cus > 0 ? cus : 256) * (per_cu > 0 ? per_cu : 1);
-    }
+    if (resident == 0) resident = resident_blocks((const void*)kern, NW * 64, lds);
     const long long nblk = (n + NW * 32 * RS - 1) / (NW * 32 * RS);
     // list mode: the row count is on the device - every resident slot launches
     const unsigned grid = (unsigned)(nblk < resident && !rlist ? nblk : resident);

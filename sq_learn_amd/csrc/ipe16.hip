@@ -45,14 +45,11 @@
 // lane c16 of a 16-lane group sums f = c16, c16 + 16, ... by fmaf in order,
 // then an xor tree over the 16 lanes (ipe_hint_kernel's order).
 #include "ipe_law.h"
+#include "f16_tile.h"
 #include <cmath>
-#include <utility>
 
 namespace sq {
 namespace i16 {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // Timing-only variant builds (benchmarks/ipe16_prep_variants.py): bits of
 // SQ_IPE16_DIAG drop parts of prep - 1: the hint's sampler (thr = the fp32
@@ -65,40 +62,13 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define SQ_IPE16_DIAG 0
 #endif
 
-constexpr int kTileN = 64;    // centroids per LDS tile (estep_x64 operand)
 constexpr int kNW = 4;        // waves per workgroup (one per SIMD)
 constexpr int kRS = 2;        // row sets of 32 per wave
 constexpr int kRows = kNW * 32 * kRS;   // 256 rows per block
-constexpr int kRing = 3;      // centroid-tile LDS slots
 constexpr int kCapR = 64;     // listed pairs per row (more: dense)
 constexpr int kNLS = kCapR + 2;   // LDS row stride of the lists (uint16): no bank aliasing
 constexpr int kMaxG = 4;      // centroid groups (tiles sorted by |c|^2): one band per group
 constexpr int kFireCap = 7;   // listed fires per row (more: dense); [0] of a row's record = count
-
-SQ_DEV float vmin(float a, float b) {
-  float r;
-  asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-SQ_DEV float and_or(float a, uint32_t m, uint32_t q) {
-  float r;
-  asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(m), "v"(q));
-  return r;
-}
-SQ_DEV float vmed3(float a, float b, float c) {
-  float r;
-  asm("v_med3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
-}
-
-template <typename F, int... I>
-SQ_DEV void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, typename F>
-SQ_DEV void static_for(F&& f) {
-  static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
 
 // the row-sorted packed best: (D~ bits, tie key with the centroid in its low
 // 14 bits) - one u64 min orders by (D~, random key), like ipe_better
@@ -806,15 +776,13 @@ struct SweepArgs {
 
 template <int KSD, bool ARGMIN, bool LB, bool GV = false>
 __global__ void __launch_bounds__(kNW * 64) ipe16_sweep_kernel(SweepArgs a) {
-  constexpr int KT = KSD + 1;                 // data k-steps + the norm step
-  constexpr int SLOT = KT * 2048;
-  constexpr int TILE_STRIDE = (2 * KSD + 1) * 2048;
-  constexpr int PIECES = SLOT / 1024;
-  constexpr int PPW = (PIECES + kNW - 1) / kNW;
+  using Ring = TileRing<KSD, kNW>;
+  static_assert(Ring::NS == 1, "one ring slot per tile");
+  constexpr int KT = Ring::KT;                // data k-steps + the norm step
   constexpr int DX = KSD * 16;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  auto buf = [&](int g) -> unsigned char* { return smem + (g % kRing) * SLOT; };
-  uint16_t* nl = reinterpret_cast<uint16_t*>(smem + (GV ? 0 : kRing * SLOT));   // [kRows][kNLS]
+  auto buf = [&](int g) -> unsigned char* { return Ring::buf(smem, g); };
+  uint16_t* nl = reinterpret_cast<uint16_t*>(smem + (GV ? 0 : Ring::BYTES));   // [kRows][kNLS]
   int* ncnt = reinterpret_cast<int*>(nl + kRows * kNLS);                  // [kRows]
   int* shint = ncnt + kRows;                                              // [kRows]
   float* sband = reinterpret_cast<float*>(shint + kRows);                 // [kRows][G][2]
@@ -841,24 +809,8 @@ __global__ void __launch_bounds__(kNW * 64) ipe16_sweep_kernel(SweepArgs a) {
   while ((1 << qbits) < 2 * n_tiles) ++qbits;
   const uint32_t keep = ~((1u << (qbits + 5)) - 1u);
 
-  auto stage = [&](int U) {
-    if constexpr (GV) return;
-    const int t = U % n_tiles;
-    const unsigned char* tile = reinterpret_cast<const unsigned char*>(a.C) + (size_t)t * TILE_STRIDE;
-    unsigned char* dst = buf(U);
-#pragma unroll
-    for (int i = 0; i < PPW; ++i) {
-      const int p = wave + kNW * i < PIECES ? wave + kNW * i : PIECES - 1;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)(tile + p * 1024 + lane * 16),
-          (__attribute__((address_space(3))) void*)(dst + p * 1024), 16, 0, 0);
-    }
-  };
-  auto sync_tile = [&]() {
-    if constexpr (GV) return;
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW) : "memory");
-    __builtin_amdgcn_s_barrier();
-  };
+  auto stage = [&](int U) { if constexpr (!GV) Ring::stage(a.C, smem, U, n_tiles); };
+  auto sync_tile = [&]() { if constexpr (!GV) Ring::sync(); };
   // rows of the block: set st of wave w, row rl of the set's 32
   auto row_of = [&](long long b, int st, int rl) -> long long {
     return b * kRows + (wave * kRS + st) * 32 + rl;
@@ -866,21 +818,13 @@ __global__ void __launch_bounds__(kNW * 64) ipe16_sweep_kernel(SweepArgs a) {
   f16x8 ah[kRS][KSD];
   auto load_a = [&](long long b) {
     if constexpr (GV) return;
-#pragma unroll
-    for (int st = 0; st < kRS; ++st) {
-      long long r = row_of(b, st, r32);
-      r = R(r < n ? r : n - 1);
-      const _Float16* xr = a.Xh + (size_t)r * DX + half * 8;
-#pragma unroll
-      for (int ks = 0; ks < KSD; ++ks) ah[st][ks] = *reinterpret_cast<const f16x8*>(xr + ks * 16);
-    }
+    sq::load_a(ah, half, [&](int st) {
+      const long long r = row_of(b, st, r32);
+      return a.Xh + (size_t)R(r < n ? r : n - 1) * DX;
+    });
   };
-  f16x8 aug = (f16x8)0;
-  if (half == 0) { aug[0] = aug[1] = aug[2] = (_Float16)1.0f; }
-  const int lane_off = (half * 64 + r32) * 16;
-  auto frag = [&](const unsigned char* cur, int g) -> f16x8 {
-    return *reinterpret_cast<const f16x8*>(cur + lane_off + (g / KT) * 512 + (g % KT) * 2048);
-  };
+  const f16x8 aug = aug_frag(half);
+  const int lane_off = f16op::lane_off(half, r32);
   // per-lane state: the 16 rows' band edges per set (screen) / running
   // packed minima (argmin); the near bits of the last epilogue
   // lower band edge per register (row); the upper edge per row set: the
@@ -893,7 +837,7 @@ __global__ void __launch_bounds__(kNW * 64) ipe16_sweep_kernel(SweepArgs a) {
   // near bits of the last epilogue (bit 16 st + i: register (st, i)); rows
   // whose list is full are muted (dense: no more pushes from this lane)
   uint32_t nb = 0, mute = 0;
-  auto rl_of = [&](int i) { return (i & 3) + 8 * (i >> 2) + 4 * half; };
+  auto rl_of = [&](int i) { return acc_row(i, half); };
   // one value of the previous half-tile (o), half-tile index q = 2 t + h
   auto epi = [&](int st, int i, float v, uint32_t q) {
     if constexpr (ARGMIN) {
@@ -905,11 +849,10 @@ __global__ void __launch_bounds__(kNW * 64) ipe16_sweep_kernel(SweepArgs a) {
     }
   };
   typedef f32x16 Acc[kRS];
-  constexpr int PFD = 2, NB = PFD + 1;
-  f16x8 bq[NB];
+  constexpr int PFD = 2;   // B-fragment read distance (k-steps)
+  f16x8 bq[PFD + 1];
   auto pass = [&](auto H_, const unsigned char* cur, Acc& acc, const Acc& o, uint32_t qo,
                   bool do_epi) {
-    constexpr int h = decltype(H_)::value;
     if constexpr (GV) {
       // this half-tile's values (half-tile index qo + 1) of the block's rows,
       // then the previous half-tile's epilogue
@@ -922,28 +865,9 @@ __global__ void __launch_bounds__(kNW * 64) ipe16_sweep_kernel(SweepArgs a) {
           p = p < n ? p : n - 1;
           acc[st][i] = a.V[(size_t)p * a.k_pad + col];
         }
-      if (do_epi) {
-#pragma unroll
-        for (int e = 0; e < 16 * kRS; ++e) epi(e / 16, e % 16, o[e / 16][e % 16], qo);
-      }
-      return;
-    }
-#pragma unroll
-    for (int st = 0; st < kRS; ++st) acc[st] = (f32x16){0};
-#pragma unroll
-    for (int ks = 0; ks < KT; ++ks) {
-      const int g = h * KT + ks;
-      if (g + PFD < 2 * KT) bq[(g + PFD) % NB] = frag(cur, g + PFD);
-#pragma unroll
-      for (int st = 0; st < kRS; ++st)
-        acc[st] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ks < KSD ? ah[st][ks] : aug, bq[g % NB],
-                                                         acc[st], 0, 0, 0);
-      if (do_epi) {
-#pragma unroll
-        for (int e = (ks * 16 * kRS) / KT; e < ((ks + 1) * 16 * kRS) / KT; ++e)
-          epi(e / 16, e % 16, o[e / 16][e % 16], qo);
-      }
-      __builtin_amdgcn_sched_barrier(0);
+      if (do_epi) half_drain(o, qo, epi);
+    } else {
+      half_pass<decltype(H_)::value>(cur, lane_off, ah, aug, bq, acc, o, qo, do_epi, epi);
     }
   };
   // near pairs of the half-tile just screened (operand column jp): each lane
@@ -1085,11 +1009,8 @@ __global__ void __launch_bounds__(kNW * 64) ipe16_sweep_kernel(SweepArgs a) {
     for (int t = 0; t < n_tiles; ++t) {
       if (t > 0) colc(64 * (t - 1) + 32 + r32, jcA, nyA);
       colc(64 * t + r32, jcB, nyB);
-      stage(U + kRing - 1);
-      if constexpr (!GV) {
-#pragma unroll
-        for (int j = 0; j < PFD; ++j) bq[j] = frag(buf(U), j);
-      }
+      stage(U + Ring::RING - 1);
+      if constexpr (!GV) tile_prime<KT>(buf(U), lane_off, bq);
       pass(std::integral_constant<int, 0>{}, buf(U), cA, cB, (uint32_t)(2 * t - 1), t > 0);
       flush_near(blk, jcA, nyA, cB);
       // tile t's values (epilogues from the next pass on) use its group's bands
@@ -1101,10 +1022,7 @@ __global__ void __launch_bounds__(kNW * 64) ipe16_sweep_kernel(SweepArgs a) {
     }
     colc(64 * (n_tiles - 1) + 32 + r32, jcA, nyA);
     load_a(blk + gridDim.x);   // clamped rows: unconditional
-#pragma unroll
-    for (int st = 0; st < kRS; ++st)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) epi(st, i, cB[st][i], (uint32_t)(2 * n_tiles - 1));
+    half_drain(cB, (uint32_t)(2 * n_tiles - 1), epi);
     flush_near(blk, jcA, nyA, cB);
 
     if constexpr (ARGMIN) {
@@ -1238,10 +1156,10 @@ __global__ void __launch_bounds__(kNW * 64) ipe16_sweep_kernel(SweepArgs a) {
 // ------------------------------------------------------------------ values
 // Wide rows (d_pad > 256: the A fragments of a row set no longer fit in
 // VGPRs next to the sweep's epilogue state): the sweep's pass values are
-// computed here first - per wave 32 positions x one 64-centroid tile, the
-// SAME operands in the same k-step order through the same MFMA from zero, so
-// every value equals the resident-fragment sweep's bit for bit - and the
-// GV sweep reads them instead of running its MFMAs.  V [n][k_pad] fp32, in
+// computed here first - per wave 32 positions x one 64-centroid tile by
+// tile_from_zero (f16_tile.h: the pass's own fragment helpers in its k-step
+// order, so every value equals the resident-fragment sweep's bit for bit) -
+// and the GV sweep reads them instead of running its MFMAs.  V [n][k_pad] fp32, in
 // the accumulator layout (register i of lane (half, r32): row (i & 3) +
 // 8 (i >> 2) + 4 half of the wave's 32, column 64 t + 32 h + r32).
 struct ValuesArgs {
@@ -1262,23 +1180,14 @@ __global__ void __launch_bounds__(256) ipe16_values_kernel(ValuesArgs a) {
   const int t = blockIdx.y;
   const long long p = p0 + r32 < n ? p0 + r32 : n - 1;
   const long long r = a.rows ? (long long)a.rows[p] : p;
-  const int KT = a.ksd + 1;
-  const _Float16* xr = a.Xh + (size_t)r * (a.ksd * 16) + half * 8;
   const unsigned char* tile = reinterpret_cast<const unsigned char*>(a.C) +
-                              (size_t)t * (2 * a.ksd + 1) * 2048 + (half * 64 + r32) * 16;
-  f16x8 aug = (f16x8)0;
-  if (half == 0) { aug[0] = aug[1] = aug[2] = (_Float16)1.0f; }
-  f32x16 c0 = (f32x16){0}, c1 = (f32x16){0};
-  for (int ks = 0; ks < KT; ++ks) {
-    const f16x8 av = ks < a.ksd ? *reinterpret_cast<const f16x8*>(xr + ks * 16) : aug;
-    const f16x8 b0 = *reinterpret_cast<const f16x8*>(tile + ks * 2048);
-    const f16x8 b1 = *reinterpret_cast<const f16x8*>(tile + 512 + ks * 2048);
-    c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, b0, c0, 0, 0, 0);
-    c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, b1, c1, 0, 0, 0);
-  }
+                              (size_t)t * f16op::tile_bytes(a.ksd);
+  f32x16 c0, c1;
+  tile_from_zero(tile, f16op::lane_off(half, r32), a.Xh + (size_t)r * (a.ksd * 16), half, a.ksd,
+                 c0, c1);
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
-    const long long q = p0 + (i & 3) + 8 * (i >> 2) + 4 * half;
+    const long long q = p0 + acc_row(i, half);
     if (q < n) {
       float* vr = a.V + (size_t)q * a.k_pad + 64 * t + r32;
       vr[0] = c0[i];
@@ -1600,9 +1509,8 @@ using namespace sq::i16;
 
 template <int KSD, bool ARGMIN, bool LB, bool GV = false>
 static int launch_sweep(const SweepArgs& a, hipStream_t st) {
-  constexpr int SLOT = (KSD + 1) * 2048;
-  const size_t lds = (GV ? 0 : kRing * (size_t)SLOT) + (size_t)kRows * kNLS * 2 + 2 * kRows * 4 +
-                     (size_t)kRows * kMaxG * 2 * 4 + (size_t)kRows * 6 * 4;
+  const size_t lds = (GV ? 0 : (size_t)TileRing<KSD, kNW>::BYTES) + (size_t)kRows * kNLS * 2 +
+                     2 * kRows * 4 + (size_t)kRows * kMaxG * 2 * 4 + (size_t)kRows * 6 * 4;
   auto kern = ipe16_sweep_kernel<KSD, ARGMIN, LB, GV>;
   static int attr = 0;
   if (!attr) {
@@ -1614,13 +1522,7 @@ static int launch_sweep(const SweepArgs& a, hipStream_t st) {
   }
   if (attr == 2) return (int)hipErrorNotSupported;
   static int resident = 0;
-  if (resident == 0) {
-    int dev = 0, cus = 0, per_cu = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kern, kNW * 64, lds);
-    resident = (cus > 0 ? cus : 256) * (per_cu > 0 ? per_cu : 1);
-  }
+  if (resident == 0) resident = resident_blocks((const void*)kern, kNW * 64, lds);
   const long long nblk = (a.n + kRows - 1) / kRows;
   const unsigned grid = (unsigned)(nblk < resident ? nblk : resident);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(kNW * 64), lds, st, a);

@@ -27,11 +27,11 @@
 #include "common.h"
 #include "fejer.h"
 #include "band.h"
+#include "f16_tile.h"
 
 namespace sq {
 
 typedef __attribute__((ext_vector_type(8))) short bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 constexpr int kBN = 64;                  // centroids per LDS tile
 constexpr float kBig = 3.0e38f;
@@ -1665,12 +1665,10 @@ __global__ void __launch_bounds__(256) centroid_finalize_kernel(
   __shared__ double red[4];
   __shared__ float redf[4];
   __shared__ double redn[4];
-  // fp16 operand: per 64-centroid tile [hi chunks: d_pad/8 + 2][lo chunks: d_pad/8]
-  const int dch = d_pad / 8;
-  _Float16* Cf = C_f16 ? C_f16 + (size_t)(j >> 6) * (2 * dch + 2) * 512 + (size_t)(j & 63) * 8
-                       : nullptr;
-  auto hi16 = [&](int c) -> _Float16& { return Cf[(size_t)(c >> 3) * 512 + (c & 7)]; };
-  auto lo16 = [&](int c) -> _Float16& { return Cf[(size_t)(dch + 2 + (c >> 3)) * 512 + (c & 7)]; };
+  // fp16 operand (layout: f16_tile.h)
+  _Float16* Cf = C_f16 ? C_f16 + f16op::row_base(d_pad, j) : nullptr;
+  auto hi16 = [&](int c) -> _Float16& { return Cf[f16op::hi_off(c)]; };
+  auto lo16 = [&](int c) -> _Float16& { return Cf[f16op::lo_off(d_pad, c)]; };
   // chunk-major E-step operand (see estep_kernel): -2 c, then [hi, mid, lo]
   // of ||bf16(c)||^2 in the augmented chunk, zeros after
   const int cpr = d_pad / 8 + 2;
@@ -1719,7 +1717,7 @@ __global__ void __launch_bounds__(256) centroid_finalize_kernel(
     if (Cf) { hi16(c) = fh; lo16(c) = fl; }
   }
   if (C_bf16) for (int c = d_pad + 3 + tid; c < d_pad + 16; c += 256) at(c) = 0;
-  if (Cf) for (int c = d_pad + 3 + tid; c < d_pad + 16; c += 256) hi16(c) = (_Float16)0.0f;
+  if (Cf) for (int c = d_pad + f16op::kNormElems + tid; c < d_pad + 16; c += 256) hi16(c) = (_Float16)0.0f;
   sh = wave_sum(sh);
   nn = wave_sum(nn);
   nn64 = wave_sum(nn64);

@@ -25,8 +25,10 @@ from test_ipe16_skip_gpu import _blobs, _two_steps
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("d", [64, 256])
+@pytest.mark.parametrize("d", [16, 24, 64, 256])
 def test_values_pass_bit_identical_to_resident_sweep(cuda, monkeypatch, d):
+    # d = 16: one data k-step (KT = 2, shorter than the pass's 3-register B
+    # ring); d = 24: two, the second half padding ahead of the norm step
     X, C = _blobs(3, d=d, k=40)
     Xt, Ct = torch.tensor(X, device=cuda), torch.tensor(C, device=cuda)
     outs = []
