@@ -81,6 +81,16 @@ __attribute__((weak)) int sq_forest_predict(const void*, const void*, const void
 __attribute__((weak)) int sq_elkan_step(const void*, const void*, const void*, const void*,
                                         const void*, void*, void*, void*, long long, int, int,
                                         int, int, void*);
+// spkmeans.hip
+__attribute__((weak)) int sq_sp_row_norms(const void*, const void*, void*, long long, void*);
+__attribute__((weak)) int sq_sp_estep(const void*, const void*, const void*, const void*,
+                                      const void*, const void*, long long, long long, int, int,
+                                      int, int, double, unsigned, unsigned, unsigned, unsigned,
+                                      long long, void*, void*, void*, void*, void*, long long,
+                                      void*);
+__attribute__((weak)) int sq_sp_mstep(const void*, const void*, const void*, const void*,
+                                      const void*, long long, int, int, int, int, void*, void*,
+                                      void*, void*, void*);
 // failure.hip
 __attribute__((weak)) int sq_failure_inject(void*, long long, int, double, int, unsigned, unsigned,
                                             unsigned, unsigned, unsigned, unsigned, unsigned,
@@ -449,6 +459,38 @@ static PyObject* py_elkan_step(PyObject*, PyObject* a) {
                            init, P(st)));
 }
 
+static PyObject* py_sp_row_norms(PyObject*, PyObject* a) {
+  unsigned long long ip, da, xn, st; long long n;
+  if (!PyArg_ParseTuple(a, "KKKLK", &ip, &da, &xn, &n, &st)) return nullptr;
+  CHECK(sq_sp_row_norms)
+  return ret(sq_sp_row_norms(P(ip), P(da), P(xn), n, P(st)));
+}
+
+static PyObject* py_sp_estep(PyObject*, PyObject* a) {
+  unsigned long long ip, ix, da, CT, cn, xn, lab, mind, part, inr, out, st;
+  long long r0, r1, roff, ldo; int d, k, kp, mode; double delta; unsigned k0, k1, s0, s1;
+  if (!PyArg_ParseTuple(a, "KKKKKKLLiiiidIIIILKKKKKLK", &ip, &ix, &da, &CT, &cn, &xn, &r0, &r1,
+                        &d, &k, &kp, &mode, &delta, &k0, &k1, &s0, &s1, &roff, &lab, &mind,
+                        &part, &inr, &out, &ldo, &st))
+    return nullptr;
+  CHECK(sq_sp_estep)
+  int rc; Py_BEGIN_ALLOW_THREADS
+  rc = sq_sp_estep(P(ip), P(ix), P(da), P(CT), P(cn), P(xn), r0, r1, d, k, kp, mode, delta, k0,
+                   k1, s0, s1, roff, P(lab), P(mind), P(part), P(inr), P(out), ldo, P(st));
+  Py_END_ALLOW_THREADS
+  return ret(rc);
+}
+
+static PyObject* py_sp_mstep(PyObject*, PyObject* a) {
+  unsigned long long ip, ix, da, lab, w, qs, qc, sums, cnt, st; long long n; int d, k, xe, we;
+  if (!PyArg_ParseTuple(a, "KKKKKLiiiiKKKKK", &ip, &ix, &da, &lab, &w, &n, &d, &k, &xe, &we, &qs,
+                        &qc, &sums, &cnt, &st))
+    return nullptr;
+  CHECK(sq_sp_mstep)
+  return ret(sq_sp_mstep(P(ip), P(ix), P(da), P(lab), P(w), n, d, k, xe, we, P(qs), P(qc),
+                         P(sums), P(cnt), P(st)));
+}
+
 static PyObject* py_failure_inject(PyObject*, PyObject* a) {
   unsigned long long lab, cnt, lb, corr, mind, X, C, st; long long n, roff, ldx; int k, R, ldc, d;
   double p;
@@ -746,6 +788,9 @@ static PyMethodDef methods[] = {
     {"band_select_rows", py_band_select_rows, METH_VARARGS, "device-driven overflow fallback"},
     {"pairwise_reduce", py_pairwise_reduce, METH_VARARGS, "L1 / chi2 / chebyshev / minkowski tiles"},
     {"elkan_step", py_elkan_step, METH_VARARGS, "Elkan bounded k-means assignment"},
+    {"sp_row_norms", py_sp_row_norms, METH_VARARGS, "CSR squared row norms (fp64)"},
+    {"sp_estep", py_sp_estep, METH_VARARGS, "CSR E-step: delta-band labels / gram / distances"},
+    {"sp_mstep", py_sp_mstep, METH_VARARGS, "CSR cluster sums (64-bit fixed-point atomics)"},
     {"failure_inject", py_failure_inject, METH_VARARGS, "Bernoulli estimation failure + resampling"},
     {"tomography", py_tomography, METH_VARARGS, "batched shot-based vector tomography"},
     {"mnom_segments", py_mnom_segments, METH_VARARGS, "segmented multinomial (long vectors)"},

@@ -191,3 +191,98 @@ def check_n_features(est, data):
         raise ValueError(f"X has {data.d} features, but {type(est).__name__} is expecting "
                          f"{n_in} features as input.")
     return data
+
+
+class SparseData:
+    """A CSR matrix on the compute device (single process): ``indptr``
+    (int64), ``indices`` (int32) and ``data`` (fp32 on GPU, fp64 on CPU - the
+    dense dtype policy), canonical (sorted column indices, no duplicates;
+    explicitly stored zeros are kept)."""
+
+    def __init__(self, indptr, indices, data, shape):
+        self.indptr = indptr
+        self.indices = indices
+        self.data = data
+        self.shape = (int(shape[0]), int(shape[1]))
+        self.nnz = int(data.numel())
+        self.n_global = self.shape[0]
+        self.row_offset = 0
+        self.comm = Comm(None)
+        self.source_kind = "sparse"
+        self._rows = None
+
+    @property
+    def n_local(self):
+        return self.shape[0]
+
+    @property
+    def d(self):
+        return self.shape[1]
+
+    @property
+    def device(self):
+        return self.data.device
+
+    def row_ids(self):
+        """Row index of every stored value (int64, cached)."""
+        if self._rows is None:
+            cnt = self.indptr[1:] - self.indptr[:-1]
+            self._rows = torch.repeat_interleave(
+                torch.arange(self.shape[0], dtype=torch.int64, device=self.device), cnt,
+                output_size=self.nnz)
+        return self._rows
+
+    def dense_rows(self, s, e, dtype=torch.float64):
+        """Rows [s, e) as a dense (e - s, d) tensor of ``dtype``."""
+        lo, hi = int(self.indptr[s]), int(self.indptr[e])
+        out = torch.zeros((e - s) * self.d, dtype=dtype, device=self.device)
+        if hi > lo:
+            flat = (self.row_ids()[lo:hi] - s) * self.d + self.indices[lo:hi].to(torch.int64)
+            out.index_add_(0, flat, self.data[lo:hi].to(dtype))
+        return out.view(e - s, self.d)
+
+    def gather_dense(self, rows, dtype=torch.float64):
+        """The given rows (any order, repeats allowed) as a dense tensor."""
+        rows = [int(r) for r in np.asarray(rows).reshape(-1)]
+        out = torch.zeros((len(rows), self.d), dtype=dtype, device=self.device)
+        for t, r in enumerate(rows):
+            lo, hi = int(self.indptr[r]), int(self.indptr[r + 1])
+            if hi > lo:
+                out[t].index_add_(0, self.indices[lo:hi].to(torch.int64),
+                                  self.data[lo:hi].to(dtype))
+        return out
+
+
+def as_sparse_data(X, device=None):
+    """Validate a ``scipy.sparse`` matrix and place it on the device as CSR.
+    The caller's matrix is never mutated (sorting / duplicate summing run on a
+    copy)."""
+    import scipy.sparse as sp
+    if not sp.issparse(X):
+        raise TypeError("as_sparse_data expects a scipy.sparse matrix")
+    dev = resolve_device(device)
+    A = X.tocsr()                      # CSR input: no copy yet
+    if not A.has_canonical_format:
+        if A is X:
+            A = A.copy()
+        A.sum_duplicates()
+        A.sort_indices()
+    n, d = A.shape
+    if n < 1:
+        raise ValueError(f"Found array with {n} sample(s) (shape={A.shape}) while a minimum of 1 "
+                         "is required.")
+    if d < 1:
+        raise ValueError(f"Found array with {d} feature(s) (shape={A.shape}) while a minimum of 1 "
+                         "is required.")
+    if d >= 2 ** 31:
+        raise ValueError("sparse input supports fewer than 2^31 features")
+    if not np.isfinite(A.data).all():
+        raise ValueError("Input contains NaN, infinity or a value too large for dtype('float64').")
+    if A.nnz and (A.indices.min() < 0 or A.indices.max() >= d):
+        raise ValueError("CSR column index out of range")
+    # a fresh array in the compute dtype: the container never aliases the caller's values
+    vals = torch.from_numpy(np.array(A.data, dtype=np.float32 if dev.type == "cuda"
+                                     else np.float64))
+    return SparseData(torch.as_tensor(A.indptr.astype(np.int64)).to(dev),
+                      torch.as_tensor(A.indices.astype(np.int32)).to(dev),
+                      vals.to(dev).contiguous(), (n, d))

@@ -11,6 +11,8 @@ distances); 'auto' / 'full' / 'lloyd' run the fused MFMA Lloyd engine,
 which on MI355X beats bounds at d >= 64.  The reference's
 'auto' picks Elkan for dense data: the labels agree (both are the exact
 argmin), only the cost differs.
+A scipy sparse matrix runs the CSR engine (``_sparse.py``, HIP kernels
+``csrc/spkmeans.hip``): uncentred, fp64 centres, 'elkan' runs 'full'.
 Empty clusters are relocated to the rows farthest from their centres, like
 the reference (``_k_means_fast.pyx:162-200``; per-shard top-e + one
 all-gather when row-sharded).
@@ -20,6 +22,7 @@ import warnings
 
 import numpy as np
 import torch
+from scipy.sparse import issparse
 
 from ...base import BaseEstimator, ClusterMixin, TransformerMixin
 from ...exceptions import ConvergenceWarning
@@ -30,6 +33,7 @@ from .._data import as_data, global_mean_var, Data
 from ._init import kmeans_plusplus as _kpp, kmeans_parallel as _kpar, random_init
 from ._lloyd import LloydEngine
 from ._elkan import ElkanEngine
+from . import _sparse
 from ...ops import kmeans as K
 
 
@@ -67,6 +71,8 @@ class KMeans(TransformerMixin, ClusterMixin, BaseEstimator):
         return self.gemm_precision or get_config()["gemm_precision"]
 
     def fit(self, X, y=None, sample_weight=None):
+        if issparse(X):
+            return _sparse.kmeans_fit(self, X, sample_weight)
         data = as_data(X, device=self.device, copy=self.copy_x)
         if self.n_init <= 0:
             raise ValueError(f"n_init should be > 0, got {self.n_init} instead.")
@@ -174,12 +180,16 @@ class KMeans(TransformerMixin, ClusterMixin, BaseEstimator):
         return data, torch.as_tensor(self.cluster_centers_).to(data.device)
 
     def predict(self, X, sample_weight=None):
+        if issparse(X):
+            return _sparse.predict(self, X)
         data, C = self._data_and_centers(X)
         Xf = data.X.double() if data.device.type == "cpu" else data.X.float()
         D = K.distances_torch(Xf, C.to(Xf.dtype))
         return to_numpy(torch.argmin(D, 1)).astype(np.int32)
 
     def transform(self, X):
+        if issparse(X):
+            return _sparse.transform(self, X)
         data, C = self._data_and_centers(X)
         Xf = data.X.double() if data.device.type == "cpu" else data.X.float()
         return to_numpy(torch.sqrt(K.distances_torch(Xf, C.to(Xf.dtype))))
@@ -188,6 +198,8 @@ class KMeans(TransformerMixin, ClusterMixin, BaseEstimator):
         return self.fit(X, sample_weight=sample_weight).transform(X)
 
     def score(self, X, y=None, sample_weight=None):
+        if issparse(X):
+            return _sparse.score(self, X, sample_weight)
         data, C = self._data_and_centers(X)
         Xf = data.X.double() if data.device.type == "cpu" else data.X.float()
         D = K.distances_torch(Xf, C.to(Xf.dtype))

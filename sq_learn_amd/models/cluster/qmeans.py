@@ -20,6 +20,10 @@ Parameters keep the reference's names and defaults.  Intentional deviations
 * ``multiprocess`` is accepted and ignored - every (sample, centroid) pair is
   processed by one batched GPU kernel instead of a process pool.
 
+Sparse input (a scipy sparse matrix) runs the quantum model on CSR rows
+(``_sparse.py``, ``csrc/spkmeans.hip``) where the reference warns and falls
+back to the classical iteration; the data stay uncentred.
+
 Framework additions: ``device``, ``gemm_precision`` ('bf16': fused bf16
 MFMA kernel, d <= 256, band edge bf16-accurate; 'fp32': the certified E-step - an
 fp16 MFMA filter whose error bound is certified against fp64, multi-candidate
@@ -32,6 +36,7 @@ import warnings
 
 import numpy as np
 import torch
+from scipy.sparse import issparse
 
 from ...base import BaseEstimator, ClusterMixin, TransformerMixin
 from ...exceptions import ConvergenceWarning
@@ -43,6 +48,7 @@ from .._data import as_data, check_n_features, global_mean_var, prelude_stats
 from ...utils.checkpoint import Checkpointer, rs_state_from_tensors, rs_state_to_tensors
 from ._init import kmeans_parallel, kmeans_plusplus, kmeans_plusplus_restarts, random_init
 from ._lloyd import LloydEngine
+from . import _sparse
 from ...ops import kmeans as K
 from ...quantum.fejer import median_repetitions
 from ...quantum import cost_model
@@ -168,6 +174,8 @@ class QMeans(TransformerMixin, ClusterMixin, BaseEstimator):
     # ------------------------------------------------------------------ fit
     def fit(self, X, y=None, sample_weight=None):
         """Compute q-means clustering (``_dmeans.py:1211-1325``)."""
+        if issparse(X):
+            return _sparse.qmeans_fit(self, X, sample_weight)
         data = as_data(X, device=self.device, copy=self.copy_x)
         self._check_params(data)
         self.n_features_in_ = data.d
@@ -398,6 +406,8 @@ class QMeans(TransformerMixin, ClusterMixin, BaseEstimator):
 
     # -------------------------------------------------------------- predict
     def _assign(self, X, delta):
+        if issparse(X):
+            return _sparse.assign(self, X, delta)
         check_is_fitted(self)
         data = as_data(X, device=self.device)
         if data.d != self.n_features_in_:
@@ -432,6 +442,8 @@ class QMeans(TransformerMixin, ClusterMixin, BaseEstimator):
 
     def transform(self, X):
         """Euclidean distances to the centres (classical path, like the reference)."""
+        if issparse(X):
+            return _sparse.transform(self, X)
         check_is_fitted(self)
         data = check_n_features(self, as_data(X, device=self.device))
         C = torch.as_tensor(self.cluster_centers_).to(data.device)
@@ -451,6 +463,9 @@ class QMeans(TransformerMixin, ClusterMixin, BaseEstimator):
         """Quantum vs classical running time on a 100x100 (n, m) grid
         (``_dmeans.py:1412-1469``); returns (q_runtime, c_runtime)."""
         check_is_fitted(self)
+        if hasattr(self, "condition_number") and self.condition_number is None:
+            raise ValueError("runtime_comparison needs condition_number, which is not computed "
+                             "for sparse input (no d x d Gram is formed)")
         n, m = np.meshgrid(np.linspace(0, n_samples, dtype=np.int64, num=100),
                            np.linspace(0, n_features, dtype=np.int64, num=100))
         q, c = cost_model.qmeans_runtime(self.n_clusters, self.n_init, self.eta,
