@@ -91,6 +91,14 @@ __attribute__((weak)) int sq_sp_estep(const void*, const void*, const void*, con
 __attribute__((weak)) int sq_sp_mstep(const void*, const void*, const void*, const void*,
                                       const void*, long long, int, int, int, int, void*, void*,
                                       void*, void*, void*);
+// spmm.hip
+__attribute__((weak)) int sq_spmm_tile_cols();
+__attribute__((weak)) int sq_spmm(const void*, const void*, const void*, const void*, const void*,
+                                  const void*, long long, int, const void*, const void*,
+                                  long long, const void*, long long, int, void*, long long,
+                                  void*, void*);
+__attribute__((weak)) int sq_sp_row_moments(const void*, const void*, void*, void*, long long,
+                                            void*);
 // failure.hip
 __attribute__((weak)) int sq_failure_inject(void*, long long, int, double, int, unsigned, unsigned,
                                             unsigned, unsigned, unsigned, unsigned, unsigned,
@@ -491,6 +499,32 @@ static PyObject* py_sp_mstep(PyObject*, PyObject* a) {
                          P(sums), P(cnt), P(st)));
 }
 
+static PyObject* py_spmm_tile_cols(PyObject*, PyObject*) {
+  CHECK(sq_spmm_tile_cols)
+  return PyLong_FromLong(sq_spmm_tile_cols());
+}
+
+static PyObject* py_spmm(PyObject*, PyObject* a) {
+  unsigned long long ip, ix, da, sr, ss, sd, lr, lp, B, out, scr, st;
+  long long nseg, nlong, ldb, ldo; int seg, l;
+  if (!PyArg_ParseTuple(a, "KKKKKKLiKKLKLiKLKK", &ip, &ix, &da, &sr, &ss, &sd, &nseg, &seg, &lr,
+                        &lp, &nlong, &B, &ldb, &l, &out, &ldo, &scr, &st))
+    return nullptr;
+  CHECK(sq_spmm)
+  int rc; Py_BEGIN_ALLOW_THREADS
+  rc = sq_spmm(P(ip), P(ix), P(da), P(sr), P(ss), P(sd), nseg, seg, P(lr), P(lp), nlong, P(B),
+               ldb, l, P(out), ldo, P(scr), P(st));
+  Py_END_ALLOW_THREADS
+  return ret(rc);
+}
+
+static PyObject* py_sp_row_moments(PyObject*, PyObject* a) {
+  unsigned long long ip, da, sm, sq, st; long long n;
+  if (!PyArg_ParseTuple(a, "KKKKLK", &ip, &da, &sm, &sq, &n, &st)) return nullptr;
+  CHECK(sq_sp_row_moments)
+  return ret(sq_sp_row_moments(P(ip), P(da), P(sm), P(sq), n, P(st)));
+}
+
 static PyObject* py_failure_inject(PyObject*, PyObject* a) {
   unsigned long long lab, cnt, lb, corr, mind, X, C, st; long long n, roff, ldx; int k, R, ldc, d;
   double p;
@@ -791,6 +825,9 @@ static PyMethodDef methods[] = {
     {"sp_row_norms", py_sp_row_norms, METH_VARARGS, "CSR squared row norms (fp64)"},
     {"sp_estep", py_sp_estep, METH_VARARGS, "CSR E-step: delta-band labels / gram / distances"},
     {"sp_mstep", py_sp_mstep, METH_VARARGS, "CSR cluster sums (64-bit fixed-point atomics)"},
+    {"spmm_tile_cols", py_spmm_tile_cols, METH_NOARGS, "columns per pass of the CSR x dense kernel"},
+    {"spmm", py_spmm, METH_VARARGS, "CSR x dense fp64 product over row segments"},
+    {"sp_row_moments", py_sp_row_moments, METH_VARARGS, "CSR per-row sum and sum of squares (fp64)"},
     {"failure_inject", py_failure_inject, METH_VARARGS, "Bernoulli estimation failure + resampling"},
     {"tomography", py_tomography, METH_VARARGS, "batched shot-based vector tomography"},
     {"mnom_segments", py_mnom_segments, METH_VARARGS, "segmented multinomial (long vectors)"},

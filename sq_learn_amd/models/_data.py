@@ -210,6 +210,9 @@ class SparseData:
         self.comm = Comm(None)
         self.source_kind = "sparse"
         self._rows = None
+        # caches of ops/sparse_linalg.py (the sparsity structure never changes)
+        self._transpose = None
+        self._segments = {}
 
     @property
     def n_local(self):

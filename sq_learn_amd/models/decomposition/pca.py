@@ -6,13 +6,15 @@ import numbers
 import warnings
 
 import numpy as np
+import scipy.sparse as sp
 import torch
 
+from ...ops import sparse_linalg
 from ...runtime.device import to_numpy
-from ...utils.extmath import stable_cumsum, _infer_dimension, fast_logdet
+from ...utils.extmath import stable_cumsum, _infer_dimension, fast_logdet, randomized_svd_sparse
 from ...utils.validation import check_is_fitted, seed_from_random_state
 from ...base import BaseEstimator, TransformerMixin
-from .._data import as_data, global_mean_var
+from .._data import Data, as_data, as_sparse_data, global_mean_var
 from ._base import _BasePCA, _as_out
 from ._svd import full_svd, truncated_svd
 
@@ -129,8 +131,14 @@ class PCA(_BasePCA):
         return {"preserves_dtype": [np.float64, np.float32]}
 
 
+# sparse input of at most this many elements is densified (the exact branch)
+_SPARSE_DENSIFY_MAX = 4e6
+
+
 class TruncatedSVD(TransformerMixin, BaseEstimator):
-    """Truncated SVD without centring (randomized, fused power iteration)."""
+    """Truncated SVD without centring (randomized, fused power iteration).
+    ``scipy.sparse`` input of any format stays sparse (CSR on the device)
+    above ``_SPARSE_DENSIFY_MAX`` elements; its outputs are numpy arrays."""
 
     def __init__(self, n_components=2, *, algorithm="randomized", n_iter=5, random_state=None,
                  tol=0.0, device=None):
@@ -146,6 +154,10 @@ class TruncatedSVD(TransformerMixin, BaseEstimator):
         return self
 
     def fit_transform(self, X, y=None):
+        if sp.issparse(X):
+            if X.shape[0] * X.shape[1] > _SPARSE_DENSIFY_MAX:
+                return self._fit_transform_sparse(X)
+            X = X.toarray()        # small: the exact branch, as the same data gets as an array
         data = as_data(X, device=self.device)
         self.n_features_in_ = data.d
         zero = torch.zeros(data.d, dtype=torch.float64, device=data.device)
@@ -171,8 +183,47 @@ class TruncatedSVD(TransformerMixin, BaseEstimator):
         self.singular_values_ = S
         return _as_out(X_t, data.source_kind)
 
+    def _fit_transform_sparse(self, X):
+        """CSR rows stay sparse: the randomized SVD over the fp64 sparse
+        products of ``ops/sparse_linalg.py`` (csrc/spmm.hip on the GPU)."""
+        if self.algorithm != "randomized":
+            raise ValueError(f"algorithm={self.algorithm!r} is not supported for sparse input of "
+                             f"more than {int(_SPARSE_DENSIFY_MAX)} elements; use "
+                             "algorithm='randomized'")
+        sd = as_sparse_data(X, device=self.device)
+        n, d = sd.shape
+        self.n_features_in_ = d
+        U, S, Vt = randomized_svd_sparse(sd, self.n_components, n_iter=self.n_iter,
+                                         seed=seed_from_random_state(self.random_state))
+        S = S.cpu().numpy()
+        self.components_ = Vt.cpu().numpy()
+        # the fitted variances are those of U S, as for dense input (the same
+        # data gives the same attributes either way)
+        tdata = Data(U * torch.as_tensor(S, dtype=U.dtype, device=U.device), n, 0, sd.comm,
+                     "numpy")
+        self.explained_variance_ = to_numpy(global_mean_var(tdata)[1])
+        # the returned rows are X V, as the reference's randomized branch
+        # (``_truncated_svd.py:190-194``): U S differs from it by the
+        # approximation error of the range finder, and X V is what
+        # ``transform`` gives for the same rows
+        X_t = sparse_linalg.sp_xw(sd, Vt.T)
+        # total column variance of the sparse X from its fp64 column moments
+        cs, css = sparse_linalg.sp_col_moments(sd)
+        mean = cs / n
+        full_var = float((css / n - mean ** 2).clamp(min=0.0).sum())
+        self.explained_variance_ratio_ = self.explained_variance_ / full_var
+        self.singular_values_ = S
+        return to_numpy(X_t)
+
     def transform(self, X):
         check_is_fitted(self)
+        if sp.issparse(X):
+            sd = as_sparse_data(X, device=self.device)
+            if sd.d != self.n_features_in_:
+                raise ValueError(f"X has {sd.d} features, but TruncatedSVD is expecting "
+                                 f"{self.n_features_in_} features as input.")
+            W = torch.as_tensor(np.ascontiguousarray(self.components_.T), dtype=torch.float64)
+            return to_numpy(sparse_linalg.sp_xw(sd, W))
         data = as_data(X, device=self.device)
         if data.d != self.n_features_in_:
             raise ValueError(f"X has {data.d} features, but TruncatedSVD is expecting "

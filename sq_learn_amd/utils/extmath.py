@@ -230,7 +230,19 @@ def randomized_svd_distributed(X_local, mean, n_components, comm, *, n_oversampl
         Zn = comm.all_reduce_(L.power_iter_local(X_local, Z.to(dev), mean)).cpu()
         Z, _ = torch.linalg.qr(Zn)
     # Y = (X - mu) Z, then CholeskyQR2: Y <- Y R^-1 twice (fp64 throughout)
-    Y = L.xw(X_local, Z.to(dev), mean=mean)
+    Y = _cholqr2_rows(L.xw(X_local, Z.to(dev), mean=mean), comm)
+    # B = Q^T (X - mu) (l x d), as (X - mu)^T Q (d x l: the tall side on the tile rows)
+    B = comm.all_reduce_(L.xtx(X_local, Y, mean_a=mean)).cpu().T
+    return _rsvd_finish(Y, B, k, comm, flip_sign)
+
+
+def _cholqr2_rows(Y, comm):
+    """Orthonormal basis of the columns of the row-sharded dense Y [n, l] by
+    two CholeskyQR passes Y <- Y R^-1 (fp64 throughout; the l x l Cholesky on
+    the host, with a diagonal jitter when it fails)."""
+    from ..ops import linalg as L
+    dev = Y.device
+    l = Y.shape[1]
     Y2 = torch.empty_like(Y)
     for _ in range(2):
         G = comm.all_reduce_(L.xtx(Y)).cpu()
@@ -244,14 +256,48 @@ def randomized_svd_distributed(X_local, mean, n_components, comm, *, n_oversampl
         Rinv = torch.linalg.solve_triangular(R, torch.eye(l, dtype=R.dtype), upper=True)
         L.xw(Y, Rinv.to(dev), upper=True, out=Y2)
         Y, Y2 = Y2, Y
-    # B = Q^T (X - mu) (l x d), as (X - mu)^T Q (d x l: the tall side on the tile rows)
-    B = comm.all_reduce_(L.xtx(X_local, Y, mean_a=mean)).cpu().T
+    return Y
+
+
+def _rsvd_finish(Y, B, k, comm, flip_sign):
+    """(U, s, Vt) from the orthonormal range basis Y [n, l] and B = Y^T A
+    [l, d] (host): the small SVD, U = Y Uhat, u-based signs."""
+    from ..ops import linalg as L
+    dev = Y.device
     Uhat, sv, Vt = torch.linalg.svd(B, full_matrices=False)
     U = L.xw(Y, Uhat[:, :k].contiguous().to(dev))
     Vt = Vt[:k].to(dev)
     if flip_sign:
         U, Vt = svd_flip_distributed(U, Vt, comm)
     return U, sv[:k].to(dev), Vt
+
+
+def randomized_svd_sparse(sd, n_components, *, n_oversamples=10, n_iter="auto", seed=0,
+                          flip_sign=True):
+    """Randomized SVD of a CSR matrix (``models._data.SparseData``, no
+    centring): the "stream" iteration of :func:`randomized_svd_distributed`
+    with its three passes over the rows replaced by the sparse products of
+    ``ops/sparse_linalg.py`` (csrc/spmm.hip on the GPU) - X Z, X^T Y and
+    X^T (X Z).  The same Philox test matrix, the same host QR per power
+    iteration, the same two CholeskyQR passes on the dense Y, the same small
+    SVD and sign rule, so on equal data it agrees with the dense path to
+    rounding.  Returns (U [n, k] fp64, s [k], Vt [k, d])."""
+    from ..ops import sparse_linalg as S
+    from ..ops.random import philox_normal
+    from ..runtime.rng import RngKey
+    n, d = sd.shape
+    k = int(n_components)
+    l = min(k + n_oversamples, d)
+    if n_iter == "auto":
+        n_iter = 7 if k < 0.1 * min(n, d) else 4
+    dev = sd.device
+    S.check_svd_memory(sd, l)
+    Z = philox_normal((d, l), RngKey(seed, "gaussian", 0), dtype=torch.float64, device="cpu")
+    for _ in range(n_iter):
+        Z, _ = torch.linalg.qr(S.sp_power_iter(sd, Z.to(dev)).cpu())
+    Y = _cholqr2_rows(S.sp_xw(sd, Z.to(dev)), sd.comm)
+    B = S.sp_xty(sd, Y).cpu().T
+    return _rsvd_finish(Y, B, k, sd.comm, flip_sign)
 
 
 # --------------------------------------------------------- PPCA dimension
