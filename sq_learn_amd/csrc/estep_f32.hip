@@ -1211,6 +1211,8 @@ struct MultiRec {
   long long* mrows_b = nullptr;    // list B (rows with a current record)
   int* count_b = nullptr;
   int* n_done = nullptr;           // list-B rows the gap screen resolved
+  long long* mrows_mv = nullptr;   // list-B rows whose label can have moved (the gap
+  int* count_mv = nullptr;         // screen: new argmin, or forwarded to the multi list)
 };
 static thread_local MultiRec g_mrec;
 // second overflow list of the dense-row 3-pass kernel (null: off) - the
@@ -1227,7 +1229,8 @@ extern "C" int sq_set_overflow2(void* rows, void* count) {
 }
 extern "C" int sq_multi_records(void* rec, void* mflag, int it_now, int it_lo, int ring,
                                 const void* dsh, const void* dq, long long dsh_stride,
-                                void* mrows_b, void* count_b, void* n_done) {
+                                void* mrows_b, void* count_b, void* n_done, void* mrows_mv,
+                                void* count_mv) {
   g_mrec.rec = (GapRec*)rec;
   g_mrec.mflag = (int*)mflag;
   g_mrec.it_now = it_now;
@@ -1239,6 +1242,9 @@ extern "C" int sq_multi_records(void* rec, void* mflag, int it_now, int it_lo, i
   g_mrec.mrows_b = (long long*)mrows_b;
   g_mrec.count_b = (int*)count_b;
   g_mrec.n_done = (int*)n_done;
+  g_mrec.mrows_mv = (long long*)mrows_mv;
+  g_mrec.count_mv = (int*)count_mv;
+  if ((mrows_mv != nullptr) != (count_mv != nullptr)) return (int)hipErrorInvalidValue;
   return (rec && (it_now < 1 || it_lo < 1 || it_lo > it_now || ring < 2 || ring > 16 || !mflag ||
                   !dsh || !dq || !mrows_b || !count_b))
              ? (int)hipErrorInvalidValue
@@ -1818,7 +1824,7 @@ __global__ void __launch_bounds__(256) gap_screen_kernel(
     long long dq_stride, float inv_alpha, float delta, int* __restrict__ labels,
     GapRec* __restrict__ rec, int* __restrict__ mflag, int it_now, int ring, int rebase_age,
     long long* __restrict__ mrows, int* __restrict__ multi_count, long long cap,
-    int* __restrict__ n_done) {
+    int* __restrict__ n_done, long long* __restrict__ mrows_mv, int* __restrict__ count_mv) {
   constexpr int LPR = 32;
   using VT = typename std::conditional<DX % 256 == 0, uint4, uint2>::type;
   constexpr int HV = (int)sizeof(VT) / 2;   // halves per vector
@@ -1835,6 +1841,32 @@ __global__ void __launch_bounds__(256) gap_screen_kernel(
   const float sub_err = sqrtf((float)DX) * 0x1p-25f * inv_alpha;
   constexpr float gam = (float)(DX + 16) * 0x1p-24f;
   uint32_t done_cnt = 0;
+  // the rows a wave appends to the multi list and to the moved list are
+  // staged in LDS and written out up to kGapStage at a time, one atomic each
+  // (measured at 10M rows, profiles/moved_rows.md: a second atomic + wait per
+  // block of 64 rows for the moved list took this kernel from 291 to 442 us;
+  // both lists staged 298 us)
+  constexpr int kGapStage = 256;
+  __shared__ long long stage_fw[4][kGapStage], stage_mv[4][kGapStage];
+  int n_fw = 0, n_mv = 0;   // wave-uniform
+  auto flush = [&](const long long* buf, int& cnt, long long* __restrict__ dst, int* counter) {
+    if (cnt == 0) return;   // wave-uniform
+    int b = 0;
+    if (lane == 0) b = atomicAdd(counter, cnt);
+    b = __shfl(b, 0, 64);
+    __builtin_amdgcn_wave_barrier();
+    for (int i = lane; i < cnt; i += 64)
+      if ((long long)b + i < cap) dst[(long long)b + i] = buf[i];
+    cnt = 0;
+  };
+  auto stage = [&](bool pred, long long row, long long* buf, int& cnt, long long* __restrict__ dst,
+                   int* counter) {
+    const unsigned long long pm = __ballot(pred);
+    if (pm == 0) return;                                    // wave-uniform
+    if (cnt + 64 > kGapStage) flush(buf, cnt, dst, counter);
+    if (pred) buf[cnt + __popcll(pm & ((1ull << lane) - 1ull))] = row;
+    cnt += __popcll(pm);
+  };
   auto rl = [](int v, int l) -> int { return __builtin_amdgcn_readlane(v, l); };
   auto rlf = [](float v, int l) -> float {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
@@ -2000,18 +2032,18 @@ __global__ void __launch_bounds__(256) gap_screen_kernel(
                                  jc[3] * (m == 3);
       mflag[g] = it_now + 2;
     }
-    // the rest -> the multi list (fp32 screen): one atomic per block
+    // the rest -> the multi list (fp32 screen)
     const bool fwd = live && !done;
-    const unsigned long long fm = __ballot(fwd);
-    if (fm) {   // wave-uniform
-      int fb = 0;
-      if (lane == 0) fb = atomicAdd(multi_count, __popcll(fm));
-      fb = __shfl(fb, 0, 64);
-      const long long se = (long long)fb + __popcll(fm & ((1ull << lane) - 1ull));
-      if (fwd && se < cap) mrows[se] = g;
-    }
+    stage(fwd, g, stage_fw[threadIdx.x >> 6], n_fw, mrows, multi_count);
+    // the rows whose label can differ from the previous iteration's (a new
+    // argmin here, or forwarded: the re-check decides) -> the moved list, so
+    // the incremental M-step walks these instead of all of list B
+    if (mrows_mv)   // kernel-uniform
+      stage(fwd || (done && m != slot), g, stage_mv[threadIdx.x >> 6], n_mv, mrows_mv, count_mv);
     done_cnt += __popcll(__ballot(done));
   }
+  flush(stage_fw[threadIdx.x >> 6], n_fw, mrows, multi_count);
+  if (mrows_mv) flush(stage_mv[threadIdx.x >> 6], n_mv, mrows_mv, count_mv);
   if (n_done && lane == 0 && done_cnt) atomicAdd(n_done, (int)done_cnt);
 }
 
@@ -2366,7 +2398,7 @@ static int launch_estep_x64(const void* Xh, const void* X, const void* C, const 
                          g_mrec.dsh_stride / (KSD * 16) * 8, 1.0f / alpha, (float)delta,
                          (int*)labels, g_mrec.rec, g_mrec.mflag, g_mrec.it_now, g_mrec.ring,
                          max(1, g_mrec.ring / 2), (long long*)mrows, (int*)multi_count, n,
-                         g_mrec.n_done);
+                         g_mrec.n_done, g_mrec.mrows_mv, g_mrec.count_mv);
     }
   }
   if (xflag) {

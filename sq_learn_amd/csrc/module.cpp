@@ -32,7 +32,7 @@ __attribute__((weak)) int sq_bounds_filter(const void*, void*, void*, const void
                                            void*, const void*, const void*, int, int, void*, void*,
                                            void*);
 __attribute__((weak)) int sq_multi_records(void*, void*, int, int, int, const void*, const void*,
-                                           long long, void*, void*, void*);
+                                           long long, void*, void*, void*, void*, void*);
 __attribute__((weak)) int sq_set_overflow2(void*, void*);
 __attribute__((weak)) int sq_shift_operand(const void*, const void*, int, int, int, int, double,
                                            void*, void*, void*, int, int, unsigned, void*);
@@ -302,13 +302,13 @@ static PyObject* py_bounds_filter(PyObject*, PyObject* a) {
 
 // the multi-row records of this thread's next certified E-steps (null: off)
 static PyObject* py_multi_records(PyObject*, PyObject* a) {
-  unsigned long long rec, mf, dsh, dq, mb, cb, nd; int now, lo, ring; long long ds;
-  if (!PyArg_ParseTuple(a, "KKiiiKKLKKK", &rec, &mf, &now, &lo, &ring, &dsh, &dq, &ds, &mb, &cb,
-                        &nd))
+  unsigned long long rec, mf, dsh, dq, mb, cb, nd, mv, cmv; int now, lo, ring; long long ds;
+  if (!PyArg_ParseTuple(a, "KKiiiKKLKKKKK", &rec, &mf, &now, &lo, &ring, &dsh, &dq, &ds, &mb, &cb,
+                        &nd, &mv, &cmv))
     return nullptr;
   CHECK(sq_multi_records)
   return ret(sq_multi_records(P(rec), P(mf), now, lo, ring, P(dsh), P(dq), ds, P(mb), P(cb),
-                              P(nd)));
+                              P(nd), P(mv), P(cmv)));
 }
 
 // the second overflow list of the dense-row 3-pass kernel (null: off)

@@ -257,6 +257,10 @@ class LloydEngine:
             R = min(max(int(os.environ.get("SQ_GAP_RING", "8")), 2), 16)
             self.mrec = torch.zeros((max(self.n, 1), 8), dtype=torch.float32, device=dev)
             self.rows_b = torch.empty(max(self.n, 1), dtype=torch.int64, device=dev)
+            # the list-B rows whose label can have moved (the gap screen lists
+            # them: new argmin, or forwarded to the multi list) - what the
+            # incremental M-step walks of list B
+            self.rows_moved = torch.empty(max(self.n, 1), dtype=torch.int64, device=dev)
             self.gsnap = torch.zeros((R, self.k, self.d_pad), dtype=torch.float32, device=dev)
             self.dsh = torch.zeros((R, self.k, self.d_pad), dtype=torch.float16, device=dev)
             self.dq = torch.zeros((R, self.k, 8), dtype=torch.float32, device=dev)
@@ -453,7 +457,8 @@ class LloydEngine:
                     R = self.dsh.shape[0]
                     K.multi_records(self.mrec, self.buf.mflag, self._rit,
                                     max(self._rlo, self._rit - R + 1), self.dsh, self.dq,
-                                    self.rows_b, self.buf.counts[5:6], self.buf.counts[4:5])
+                                    self.rows_b, self.buf.counts[5:6], self.buf.counts[4:5],
+                                    self.rows_moved, self.buf.counts[8:9])
                 else:
                     # thread-local: a previous engine's records never leak in
                     K.multi_records(None)
@@ -482,10 +487,13 @@ class LloydEngine:
                         else:
                             rows = (self.rlist, self.rcount)
                             # disjoint: unpruned rows, the filter's multi rows
-                            # (the multi list's head), list B
+                            # (the multi list's head), the rows of list B the
+                            # gap screen found moved (a list-B row it resolved
+                            # with the record's argmin kept its label; the
+                            # ones it forwards are not in the multi head)
                             self._dlists = ((self.rlist, self.rcount),
                                             (self.buf.multi_rows, self.buf.counts[7:8]),
-                                            (self.rows_b, self.buf.counts[5:6])
+                                            (self.rows_moved, self.buf.counts[8:9])
                                             if self.mrec is not None and screen else None)
                         zero = False
                     lab, mind = K.estep_x64_native(self.Xh16, self.Xf32, self.C_op, Cp, self.xn,
@@ -703,7 +711,10 @@ class LloydEngine:
         ``events`` (two CUDA events, optional) are recorded after the
         segmented reduce and after the all-reduce (phase timing)."""
         noise_key = self._key("trunc_normal")
+        # (step(): after the incremental M-step prev_labels holds these labels)
+        self._mstep_inc = False
         if self.fast and getattr(self, "incremental", False) and self.buf.corr is not None:
+            self._mstep_inc = True
             return self._mstep_incremental(labels, inertia, noise_key, events)
         if self.fast:
             with tracing.range("mstep"):
@@ -839,10 +850,14 @@ class LloydEngine:
             # E-step only its row lists (labels changed nowhere else: no
             # failure injection, statistics valid)
             # (measured: the list walk gathers, the full walk streams - a win
-            # on a 1.25M-row shard, 18.8 -> 11.5 us; even at 10M rows with
-            # ~14 % of the rows listed: SQ_DELTA_LISTS=1 forces it, 0 never)
+            # on a 1.25M-row shard, 18.8 -> 11.5 us, about even at 10M rows
+            # with ~14 % of the rows listed.  With gap records the third list
+            # holds only the list-B rows the gap screen found moved, a few
+            # per cent of list B, so the walk is the default at every size;
+            # SQ_DELTA_LISTS=1 forces it, 0 never)
             dl = os.environ.get("SQ_DELTA_LISTS")
-            use = (self.n <= 4_000_000) if dl is None else dl != "0"
+            use = ((self.n <= 4_000_000 or self.mrec is not None) if dl is None
+                   else dl != "0")
             lists = getattr(self, "_dlists", None) if (use and self.inc_valid
                                                        and not self.failure_prob > 0) else None
             self._dlists = None
@@ -1032,6 +1047,11 @@ class LloydEngine:
     def step(self):
         """One Lloyd iteration; returns (labels, scalars_tensor).
 
+        The returned labels (int32, n) are valid until the next ``step()``
+        (or ``estep`` / ``set_centers``) call: they are a view of an engine
+        buffer that the next iteration rewrites, so a caller that keeps them
+        longer clones them.
+
         With empty-cluster relocation the scalars come back as a host tensor:
         the iteration's single device->host read carries the number of
         empty clusters of the M-step's (global) counts as well, and only when
@@ -1077,12 +1097,19 @@ class LloydEngine:
             host, ev = self._sc_ring[self.it & 1]
             host.copy_(sc.reshape(-1), non_blocking=True)
             ev.record()
-            # the caller keeps this iteration's labels: a device snapshot
-            # before the next E-step rewrites the buffer
-            if self._label_snap is None or self._label_snap.shape != labels.shape:
-                self._label_snap = torch.empty_like(labels)
-            self._label_snap.copy_(labels)
-            labels = self._label_snap
+            # the caller keeps this iteration's labels while the next E-step
+            # rewrites the buffer.  After the incremental M-step prev_labels
+            # already holds them (it set prev <- labels on every row whose
+            # label differed, failure-injected ones included) and nothing
+            # writes it before the next step's M-step: no copy.  Every other
+            # M-step: a device snapshot.
+            if getattr(self, "_mstep_inc", False):
+                labels = self.prev_labels[:self.n]
+            else:
+                if self._label_snap is None or self._label_snap.shape != labels.shape:
+                    self._label_snap = torch.empty_like(labels)
+                self._label_snap.copy_(labels)
+                labels = self._label_snap
             self._pending = self._estep(self._key("band_select"))
             sc = _HostScalars(host, ev, self._on_scalars)
         elif getattr(self, "bounds", False) and torch.is_tensor(sc) and sc.numel() > 3:

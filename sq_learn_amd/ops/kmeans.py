@@ -185,8 +185,9 @@ class EStepBuffers:
         # [3-pass overflow rows, dense rows, multi rows, kept rows (filter),
         #  list-B rows resolved by the gap screen, list-B rows (filter),
         #  overflow rows of the second (3 members per lane) 3-pass,
-        #  the filter's own multi-list rows (the list's head)]
-        self.counts = torch.zeros(8, dtype=torch.int32, device=device)
+        #  the filter's own multi-list rows (the list's head),
+        #  list-B rows the gap screen found moved (new argmin or forwarded)]
+        self.counts = torch.zeros(12, dtype=torch.int32, device=device)
         self.ovf2_rows = None
         self.exact_flag = None   # the fp32 screen's hand-off flags (per multi entry)
         self.ovf_count = self.counts[0:1]
@@ -442,23 +443,32 @@ def fast_centroids_native(shift, C, nf, idx, smax_rest, cc, shift_sq=None):
 
 
 def multi_records(rec=None, mflag=None, it_now=0, it_lo=0, dsh=None, dq=None, rows_b=None,
-                  count_b=None, n_done=None):
+                  count_b=None, n_done=None, rows_moved=None, count_moved=None):
     """Set (or clear, rec=None) the gap records used by this thread's next
     certified E-steps (csrc/estep_f32.hip): the fp32 screen writes a row's
     record with base ``it_now`` (mflag = 2 + base), the bounds filter lists
     rows whose base is in [it_lo, it_now - 1] in ``rows_b`` / ``count_b``,
     the gap screen moves their records by the shift operand of their base
-    (``dsh`` [ring][k][d_pad] fp16 / ``dq`` [ring][k][8], slot base % ring)."""
+    (``dsh`` [ring][k][d_pad] fp16 / ``dq`` [ring][k][8], slot base % ring).
+    ``rows_moved`` / ``count_moved`` (optional, int64 [n] / int32 [1], the
+    count zeroed with the E-step's counters): the gap screen lists there,
+    once each, the list-B rows whose label can have changed - those it
+    resolved with a new argmin and those it forwarded to the multi list."""
     if rec is None:
-        nat.native().multi_records(0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0)
+        nat.native().multi_records(0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0)
         return
     assert rec.dtype == torch.float32 and rec.shape[-1] == 8 and mflag.dtype == torch.int32
     assert dsh.dtype == torch.float16 and dq.dtype == torch.float32 and rows_b.dtype == torch.int64
     assert dsh.dim() == 3 and dq.shape[:2] == dsh.shape[:2] and dq.shape[2] == 8
+    if rows_moved is not None:
+        assert rows_moved.dtype == torch.int64 and rows_moved.numel() >= rows_b.numel()
+        assert count_moved.dtype == torch.int32
     rc = nat.native().multi_records(rec.data_ptr(), mflag.data_ptr(), int(it_now), int(it_lo),
                                     int(dsh.shape[0]), dsh.data_ptr(), dq.data_ptr(),
                                     int(dsh.stride(0)), rows_b.data_ptr(), count_b.data_ptr(),
-                                    0 if n_done is None else n_done.data_ptr())
+                                    0 if n_done is None else n_done.data_ptr(),
+                                    0 if rows_moved is None else rows_moved.data_ptr(),
+                                    0 if rows_moved is None else count_moved.data_ptr())
     if rc:
         raise RuntimeError(f"multi_records failed (hip error {rc})")
 
