@@ -1028,6 +1028,12 @@ __global__ void __launch_bounds__(kX64Waves * 64) estep_x64_kernel(
 // Rows per workgroup = 256 PER: 4096 on large shards (one list atomic per
 // chunk), 1024 below ~4M rows so a small shard (8-GPU strong scaling: 1.25M
 // rows per rank) still spreads over >= 1024 workgroups instead of 305.
+// The two per-label tables (the fp64 shifts and the Elkan minimum cc[k nf +
+// .]) are staged in LDS up to kBfLdsK centroids (24 KiB: five workgroups per
+// CU still fit, one resident round as before) - per row two LDS reads instead
+// of two lane-divergent global gathers; above that k the rows gather them
+// from global memory.
+constexpr int kBfLdsK = 2048;
 template <int PER>
 __global__ void __launch_bounds__(256) bounds_filter_kernel(
     const int* __restrict__ labels, float* __restrict__ ub, float* __restrict__ lb,
@@ -1044,10 +1050,18 @@ __global__ void __launch_bounds__(256) bounds_filter_kernel(
   // list B, where the record is moved by the centroid shifts since b (the
   // fp16 row, 512 B), else to the multi list (fp32 screen of the fp32 row)
   __shared__ int wsum[4], wsum_b[4];
-  __shared__ int base_a, base_m, base_b;
+  __shared__ int lbase[3];                  // list positions: rlist, multi list, list B
   __shared__ double sf_s[65];               // shifts of the fast centroids, [nf] = max
+  __shared__ double sh_s[kBfLdsK];          // shift[label]
+  __shared__ float cm_s[kBfLdsK];           // cc[k nf + label]
+  const bool tab = k <= kBfLdsK;            // kernel-uniform
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   if (tid < nf) sf_s[tid] = shift[fidx[tid]];
+  if (tab)
+    for (int j = tid; j < k; j += 256) {
+      sh_s[j] = shift[j];
+      cm_s[j] = nf > 0 ? cc[(size_t)k * nf + j] : 0.0f;
+    }
   __syncthreads();
   if (tid == 0) {
     double m = 0.0;
@@ -1085,8 +1099,13 @@ __global__ void __launch_bounds__(256) bounds_filter_kernel(
 #pragma unroll
     for (int q = 0; q < B; ++q) {
       const int l = lv[q];
-      shv[q] = l >= 0 ? shift[l] : 1e300;
-      cmv[q] = (l >= 0 && nf > 0) ? cc[(size_t)k * nf + l] : 0.0f;
+      if (tab) {
+        shv[q] = l >= 0 ? sh_s[l] : 1e300;
+        cmv[q] = l >= 0 ? cm_s[l] : 0.0f;
+      } else {
+        shv[q] = l >= 0 ? shift[l] : 1e300;
+        cmv[q] = (l >= 0 && nf > 0) ? cc[(size_t)k * nf + l] : 0.0f;
+      }
     }
 #pragma unroll
     for (int q = 0; q < B; ++q) {
@@ -1165,36 +1184,36 @@ __global__ void __launch_bounds__(256) bounds_filter_kernel(
     before_b += w2 < wv ? wsum_b[w2] : 0;
     total_b += wsum_b[w2];
   }
-  if (tid == 0) {
-    base_a = (total & 0xffff) ? atomicAdd(rcount, total & 0xffff) : 0;
-    base_m = (total >> 16) ? atomicAdd(multi_count, total >> 16) : 0;
-    // the multi list's head (this pass's rows, before the sweep appends):
-    // the incremental M-step's second row list
-    if (rec_count && (total >> 16)) atomicAdd(rec_count, total >> 16);
-    base_b = total_b ? atomicAdd(count_b, total_b) : 0;
+  // lanes 0..3: one list counter each, all four atomics in flight together
+  // instead of one round trip after another (3: the multi list's head - this
+  // pass's rows, before the sweep appends: the incremental M-step's second
+  // row list)
+  if (tid < 4) {
+    const int add = tid == 0 ? (total & 0xffff) : (tid == 2 ? total_b : (total >> 16));
+    int* ctr = tid == 0 ? rcount : (tid == 1 ? multi_count : (tid == 2 ? count_b : rec_count));
+    const int at = (add && ctr) ? atomicAdd(ctr, add) : 0;
+    if (tid < 3) lbase[tid] = at;
   }
   __syncthreads();
+  // every set bit is one row: walk the bits, not the PER positions
   const int ex = before + incl - mine;
-  int pos = base_a + (ex & 0xffff);
-  for (int p = 0; p < PER && act; ++p) {
-    if (act & (1ull << p)) {
-      rlist[pos++] = c0 + (long long)p * 256 + tid;
-      act &= ~(1ull << p);
-    }
+  int pos = lbase[0] + (ex & 0xffff);
+  while (act) {
+    const int p = __ffsll((long long)act) - 1;
+    rlist[pos++] = c0 + (long long)p * 256 + tid;
+    act &= act - 1;
   }
-  int mpos = base_m + (ex >> 16);
-  for (int p = 0; p < PER && rec; ++p) {
-    if (rec & (1ull << p)) {
-      mrows[mpos++] = c0 + (long long)p * 256 + tid;
-      rec &= ~(1ull << p);
-    }
+  int mpos = lbase[1] + (ex >> 16);
+  while (rec) {
+    const int p = __ffsll((long long)rec) - 1;
+    mrows[mpos++] = c0 + (long long)p * 256 + tid;
+    rec &= rec - 1;
   }
-  int bpos = base_b + before_b + incl_b - mine_b;
-  for (int p = 0; p < PER && recb; ++p) {
-    if (recb & (1ull << p)) {
-      mrows_b[bpos++] = c0 + (long long)p * 256 + tid;
-      recb &= ~(1ull << p);
-    }
+  int bpos = lbase[2] + before_b + incl_b - mine_b;
+  while (recb) {
+    const int p = __ffsll((long long)recb) - 1;
+    mrows_b[bpos++] = c0 + (long long)p * 256 + tid;
+    recb &= recb - 1;
   }
 }
 
