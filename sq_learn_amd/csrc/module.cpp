@@ -91,6 +91,19 @@ __attribute__((weak)) int sq_sp_estep(const void*, const void*, const void*, con
 __attribute__((weak)) int sq_sp_mstep(const void*, const void*, const void*, const void*,
                                       const void*, long long, int, int, int, int, void*, void*,
                                       void*, void*, void*);
+// spminibatch.hip
+__attribute__((weak)) int sq_sp_list_estep(const void*, const void*, const void*, const void*,
+                                           const void*, const void*, const void*, long long,
+                                           long long, long long, int, int, int, const void*, void*,
+                                           void*, void*, void*, void*);
+__attribute__((weak)) int sq_sp_list_mstep(const void*, const void*, const void*, const void*,
+                                           long long, const void*, const void*, long long,
+                                           long long, int, int, int, int, void*, void*, void*);
+__attribute__((weak)) int sq_mb_update(void*, void*, void*, void*, void*, void*, int, int, int, int,
+                                       int, void*, void*, void*, void*, void*);
+__attribute__((weak)) int sq_sp_rows_dense(const void*, const void*, const void*, const void*,
+                                           const void*, long long, long long, long long, int,
+                                           void*, long long, void*);
 // spmm.hip
 __attribute__((weak)) int sq_spmm_tile_cols();
 __attribute__((weak)) int sq_spmm(const void*, const void*, const void*, const void*, const void*,
@@ -499,6 +512,47 @@ static PyObject* py_sp_mstep(PyObject*, PyObject* a) {
                          P(sums), P(cnt), P(st)));
 }
 
+static PyObject* py_sp_list_estep(PyObject*, PyObject* a) {
+  unsigned long long ip, ix, da, CT, cn, xn, rows, w, lab, mind, part, inr, st;
+  long long r0, m, n; int d, k, kp;
+  if (!PyArg_ParseTuple(a, "KKKKKKKLLLiiiKKKKKK", &ip, &ix, &da, &CT, &cn, &xn, &rows, &r0, &m, &n,
+                        &d, &k, &kp, &w, &lab, &mind, &part, &inr, &st))
+    return nullptr;
+  CHECK(sq_sp_list_estep)
+  return ret(sq_sp_list_estep(P(ip), P(ix), P(da), P(CT), P(cn), P(xn), P(rows), r0, m, n, d, k,
+                              kp, P(w), P(lab), P(mind), P(part), P(inr), P(st)));
+}
+
+static PyObject* py_sp_list_mstep(PyObject*, PyObject* a) {
+  unsigned long long ip, ix, da, rows, lab, w, qs, qc, st; long long r0, m, n; int d, k, xe, we;
+  if (!PyArg_ParseTuple(a, "KKKKLKKLLiiiiKKK", &ip, &ix, &da, &rows, &r0, &lab, &w, &m, &n, &d, &k,
+                        &xe, &we, &qs, &qc, &st))
+    return nullptr;
+  CHECK(sq_sp_list_mstep)
+  return ret(sq_sp_list_mstep(P(ip), P(ix), P(da), P(rows), r0, P(lab), P(w), m, n, d, k, xe, we,
+                              P(qs), P(qc), P(st)));
+}
+
+static PyObject* py_mb_update(PyObject*, PyObject* a) {
+  unsigned long long C, CT, cn, cnt, qs, qc, pcn, psh, sh, rec, st; int k, d, kp, xe, we;
+  if (!PyArg_ParseTuple(a, "KKKKKKiiiiiKKKKK", &C, &CT, &cn, &cnt, &qs, &qc, &k, &d, &kp, &xe, &we,
+                        &pcn, &psh, &sh, &rec, &st))
+    return nullptr;
+  CHECK(sq_mb_update)
+  return ret(sq_mb_update(P(C), P(CT), P(cn), P(cnt), P(qs), P(qc), k, d, kp, xe, we, P(pcn),
+                          P(psh), P(sh), P(rec), P(st)));
+}
+
+static PyObject* py_sp_rows_dense(PyObject*, PyObject* a) {
+  unsigned long long ip, ix, da, rows, dst, out, st; long long m, n, mo, ld; int d;
+  if (!PyArg_ParseTuple(a, "KKKKKLLLiKLK", &ip, &ix, &da, &rows, &dst, &m, &n, &mo, &d, &out, &ld,
+                        &st))
+    return nullptr;
+  CHECK(sq_sp_rows_dense)
+  return ret(sq_sp_rows_dense(P(ip), P(ix), P(da), P(rows), P(dst), m, n, mo, d, P(out), ld,
+                              P(st)));
+}
+
 static PyObject* py_spmm_tile_cols(PyObject*, PyObject*) {
   CHECK(sq_spmm_tile_cols)
   return PyLong_FromLong(sq_spmm_tile_cols());
@@ -825,6 +879,10 @@ static PyMethodDef methods[] = {
     {"sp_row_norms", py_sp_row_norms, METH_VARARGS, "CSR squared row norms (fp64)"},
     {"sp_estep", py_sp_estep, METH_VARARGS, "CSR E-step: delta-band labels / gram / distances"},
     {"sp_mstep", py_sp_mstep, METH_VARARGS, "CSR cluster sums (64-bit fixed-point atomics)"},
+    {"sp_list_estep", py_sp_list_estep, METH_VARARGS, "CSR row-list argmin E-step"},
+    {"sp_list_mstep", py_sp_list_mstep, METH_VARARGS, "CSR row-list fixed-point scatter"},
+    {"mb_update", py_mb_update, METH_VARARGS, "fused mini-batch centre update"},
+    {"sp_rows_dense", py_sp_rows_dense, METH_VARARGS, "CSR rows to dense fp64 rows"},
     {"spmm_tile_cols", py_spmm_tile_cols, METH_NOARGS, "columns per pass of the CSR x dense kernel"},
     {"spmm", py_spmm, METH_VARARGS, "CSR x dense fp64 product over row segments"},
     {"sp_row_moments", py_sp_row_moments, METH_VARARGS, "CSR per-row sum and sum of squares (fp64)"},

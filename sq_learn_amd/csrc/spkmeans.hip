@@ -21,25 +21,9 @@
 //     buffer; integer addition commutes, so the sums do not depend on the
 //     arrival order or the launch geometry.  sp_mstep_finish converts to fp64.
 #include "band.h"
+#include "sp_rows.h"
 
 namespace sq {
-
-constexpr int SP_T = 4;   // centroid sub-tiles of 64 per pass over the row
-
-SQ_DEV int bcast_i(int v, int q) { return __builtin_amdgcn_readlane(v, q); }
-SQ_DEV float bcast_f(float v, int q) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), q));
-}
-SQ_DEV double wave_min_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
-  return v;
-}
-SQ_DEV void sp_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // ------------------------------------------------------------- row norms
 __global__ void __launch_bounds__(256) sp_row_norms_kernel(
@@ -61,36 +45,6 @@ __global__ void __launch_bounds__(256) sp_row_norms_kernel(
 }
 
 // ---------------------------------------------------------------- E-step
-// acc[t] += sum over the cnt (<= 64) broadcast nonzeros of v * CT[col][j0 + lane + 64 t];
-// lanes >= cnt hold (col 0, v 0), so the 4-wide unroll may overrun cnt.
-template <int NT>
-SQ_DEV void sp_accumulate(double (&acc)[SP_T], const double* __restrict__ CTj, long long k_pad,
-                          int col, float v, int cnt) {
-  for (int q = 0; q < cnt; q += 4) {
-    const double* r0 = CTj + (long long)bcast_i(col, q) * k_pad;
-    const double* r1 = CTj + (long long)bcast_i(col, q + 1) * k_pad;
-    const double* r2 = CTj + (long long)bcast_i(col, q + 2) * k_pad;
-    const double* r3 = CTj + (long long)bcast_i(col, q + 3) * k_pad;
-    const double v0 = (double)bcast_f(v, q), v1 = (double)bcast_f(v, q + 1);
-    const double v2 = (double)bcast_f(v, q + 2), v3 = (double)bcast_f(v, q + 3);
-    double x0[NT], x1[NT], x2[NT], x3[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      x0[t] = r0[64 * t];
-      x1[t] = r1[64 * t];
-      x2[t] = r2[64 * t];
-      x3[t] = r3[64 * t];
-    }
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      acc[t] = fma(v0, x0[t], acc[t]);
-      acc[t] = fma(v1, x1[t], acc[t]);
-      acc[t] = fma(v2, x2[t], acc[t]);
-      acc[t] = fma(v3, x3[t], acc[t]);
-    }
-  }
-}
-
 // mode 0: band (labels, mind, per-wave inertia partials)
 // mode 1: gram   out_f[(i - row0) * ldo + j] = (float) x_i . c_j
 // mode 2: sqdist out_d[(i - row0) * ldo + j] = D_j
@@ -184,21 +138,6 @@ __global__ void __launch_bounds__(256) sp_estep_kernel(
   if (mode == 0 && lane == 0) part[(long long)blockIdx.x * wpb + wave] = inertia;
 }
 
-// fixed-order sum of the per-wave partials (one workgroup)
-__global__ void __launch_bounds__(256) sp_sum_parts_kernel(const double* __restrict__ part, int m,
-                                                           double* __restrict__ out) {
-  __shared__ double sh[256];
-  double a = 0.0;
-  for (int i = threadIdx.x; i < m; i += 256) a += part[i];
-  sh[threadIdx.x] = a;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[0] = sh[0];
-}
-
 // ---------------------------------------------------------------- M-step
 __global__ void __launch_bounds__(256) sp_mstep_kernel(
     const long long* __restrict__ indptr, const int* __restrict__ indices,
@@ -239,12 +178,6 @@ __global__ void __launch_bounds__(256) sp_mstep_finish_kernel(
 }  // namespace sq
 
 using namespace sq;
-
-static unsigned sp_grid(long long rows, int wpb) {
-  const long long blocks = (rows + wpb - 1) / wpb;
-  const long long cap = 256LL * 8 * 4 / wpb;   // persistent: ~8 waves per SIMD lane group per CU
-  return (unsigned)(blocks < cap ? (blocks < 1 ? 1 : blocks) : cap);
-}
 
 extern "C" int sq_sp_row_norms(const void* indptr, const void* data, void* xn, long long n,
                                void* stream) {

@@ -32,7 +32,7 @@ from ...quantum.fejer import median_repetitions
 from ...runtime.device import to_numpy
 from ...runtime.rng import RngKey
 from ...utils.validation import check_is_fitted, check_random_state, seed_from_random_state
-from .._data import as_sparse_data
+from .._data import SparseData, as_sparse_data
 from ._init import permutation_head
 
 
@@ -207,11 +207,14 @@ class SparseLloydEngine:
 
 
 # ------------------------------------------------------------------ init
-def sparse_kmeans_plusplus(sd, n_clusters, random_state, xn=None, n_local_trials=None):
+def sparse_kmeans_plusplus(sd, n_clusters, random_state, xn=None, n_local_trials=None,
+                           gather=None):
     """Sequential k-means++ on CSR rows: the torch path of
     ``_init.kmeans_plusplus`` draw for draw (``randint(n)``, then
     ``random_sample((k - 1, t))``), distances by ``sp_sqdist`` against the
-    densified candidate rows.  Returns (centres [k, d] fp64, row ids)."""
+    densified candidate rows (``gather(ids)``, default ``sd.gather_dense``).
+    Returns (centres [k, d] fp64, row ids)."""
+    gather = sd.gather_dense if gather is None else gather
     n = sd.shape[0]
     k = int(n_clusters)
     dev = sd.device
@@ -224,14 +227,14 @@ def sparse_kmeans_plusplus(sd, n_clusters, random_state, xn=None, n_local_trials
     ids = torch.empty(k, dtype=torch.int64, device=dev)
     ids[0] = center_id
     centers = torch.empty((k, sd.d), dtype=torch.float64, device=dev)
-    centers[0] = sd.gather_dense([center_id])[0]
+    centers[0] = gather([center_id])[0]
     closest = S.sp_sqdist(sd, centers[:1], xn=xn)[:, 0].contiguous()
     current_pot = closest.sum()
     for c in range(1, k):
         vals = draws[c - 1] * current_pot
         cs = torch.cumsum(closest, 0)
         pos = torch.searchsorted(cs, vals.contiguous()).clamp(0, max(n - 1, 0))
-        cands = sd.gather_dense(pos.cpu().numpy())
+        cands = gather(pos.cpu().numpy())
         newd = torch.minimum(closest[:, None], S.sp_sqdist(sd, cands, xn=xn))
         pots = newd.sum(0)
         best = torch.argmin(pots)
@@ -516,3 +519,181 @@ def qmeans_fit(est, X, sample_weight=None):
     est._engine_comm = engine.comm
     _warn_distinct(est.labels_, est.n_clusters)
     return est
+
+
+# ------------------------------------------------------ mini-batch k-means
+# Reference: ``cluster/_kmeans.py`` MiniBatchKMeans on CSR (``fit`` :1470,
+# ``partial_fit`` :1638, ``_mini_batch_step`` :1133-1150).  The loop is the
+# dense path's (``minibatch.py``), draw for draw; a step never copies or
+# densifies the batch: ``ops.sparse_kmeans.MiniBatchState`` walks the id list.
+def take_rows(sd, ids):
+    """The rows ``ids`` (any order, repeats allowed) as a new CSR container,
+    built with torch ops on the device."""
+    ids = torch.as_tensor(ids, dtype=torch.int64).to(sd.device)
+    lo = sd.indptr[ids]
+    cnt = sd.indptr[ids + 1] - lo
+    indptr = torch.zeros(ids.numel() + 1, dtype=torch.int64, device=sd.device)
+    indptr[1:] = torch.cumsum(cnt, 0)
+    total = int(indptr[-1])
+    src = torch.arange(total, dtype=torch.int64, device=sd.device) \
+        + torch.repeat_interleave(lo - indptr[:-1], cnt, output_size=total)
+    return SparseData(indptr, sd.indices[src].contiguous(), sd.data[src].contiguous(),
+                      (ids.numel(), sd.d))
+
+
+def _mb_init_centers(est, X, sd, rs, xn):
+    """``MiniBatchKMeans._init_centers`` on CSR: the same host draws."""
+    n, k = sd.shape[0], est.n_clusters
+    init = est.init
+    if hasattr(init, "__array__"):
+        C = torch.as_tensor(np.asarray(init, dtype=np.float64)).to(sd.device)
+    else:
+        idx = rs.randint(0, n, est._init_size)
+        if isinstance(init, str) and init == "k-means++":
+            sub = take_rows(sd, idx)
+            sub_xn = xn[torch.as_tensor(idx, dtype=torch.int64).to(sd.device)].contiguous()
+            C, _ = sparse_kmeans_plusplus(sub, k, rs, xn=sub_xn,
+                                          gather=lambda r: S.sp_rows_dense(sub, np.asarray(r)))
+        elif isinstance(init, str) and init == "random":
+            sel = rs.permutation(len(idx))[:k]
+            C = S.sp_rows_dense(sd, idx[sel])
+        elif callable(init):
+            C = torch.as_tensor(np.asarray(init(X.tocsr()[idx], k, rs),
+                                           dtype=np.float64)).to(sd.device)
+        else:
+            raise ValueError("init should be 'k-means++', 'random' or an ndarray, "
+                             f"got {init!r}")
+    if tuple(C.shape) != (k, sd.d):
+        raise ValueError(f"The shape of the initial centers {tuple(C.shape)} does not match the "
+                         f"number of clusters {k} / features {sd.d}.")
+    return C.double()
+
+
+def _mb_reassign(est, st, sd, rows, rs):
+    """Random reassignment of starved centres (``_mini_batch_step``
+    :1093-1117) from the batch's CSR rows; True when centres were replaced."""
+    counts = st.counts
+    m = sd.shape[0] if rows is None else rows.numel()
+    to_reassign = counts < est.reassignment_ratio * counts.max()
+    nre = int(to_reassign.sum())                      # the step's one extra read
+    if nre > 0.5 * m:
+        keep = torch.argsort(counts)[int(0.5 * m):]
+        to_reassign[keep] = False
+        nre = int(to_reassign.sum())
+    if not nre:
+        return False
+    new = torch.as_tensor(rs.choice(m, replace=False, size=nre), dtype=torch.int64).to(sd.device)
+    dst = torch.nonzero(to_reassign)[:, 0]
+    S.sp_rows_dense(sd, new if rows is None else rows[new], out=st.C, dst=dst)
+    counts[to_reassign] = counts[~to_reassign].min()
+    return True
+
+
+def _mb_state(est, sd, sw, C, counts):
+    if sd.device.type == "cuda":
+        S.check_k(est.n_clusters)
+    mx = float(sd.data.abs().max()) if sd.nnz else 0.0
+    mw = None if sw is None else (float(sw.abs().max()) if sw.numel() else 0.0)
+    return S.MiniBatchState(sd.device, C, counts, mx, mw)
+
+
+def _mb_publish(est, st):
+    est._C, est._counts = st.C, st.counts
+    est.cluster_centers_ = to_numpy(st.C.double())
+    est.counts_ = to_numpy(st.counts)
+
+
+def _mb_labels(est, sd, st, sw, xn):
+    labels, _, inertia = S.sp_list_estep(sd, st.C, None, sw, xn=xn, operand=st.operand())
+    est.labels_ = to_numpy(labels).astype(np.int32)
+    est.inertia_ = float(inertia)
+
+
+def minibatch_fit(est, X, sample_weight=None):
+    """``MiniBatchKMeans.fit`` on a scipy sparse matrix."""
+    sd = as_sparse_data(X, device=est.device)
+    n, d = sd.shape
+    est._check_params(n)
+    est.n_features_in_ = d
+    rs = check_random_state(est.random_state)
+    sw = _weights(sample_weight, sd)
+    tol = _tolerance(X, est.tol) if est.tol > 0.0 else 0.0
+    n_batches = int(np.ceil(n / est.batch_size))
+    n_iter = int(est.max_iter * n_batches)
+    k = est.n_clusters
+    xn = S.sp_row_norms(sd)
+    zeros = torch.zeros(k, dtype=torch.float64)
+    vidx = torch.as_tensor(rs.randint(0, n, est._init_size), dtype=torch.int64).to(sd.device)
+    wv = None if sw is None else sw[vidx]
+    best = None
+    for _ in range(est._n_init):
+        st = _mb_state(est, sd, sw, _mb_init_centers(est, X, sd, rs, xn), zeros)
+        st.advance(sd, xn, vidx, wv)
+        inertia = float(st.estep(sd, xn, vidx, wv)[2])
+        if best is None or inertia < best[0]:
+            best = (inertia, st)
+    st = best[1]
+    min_count = float(st.counts.min())
+    ctx = {}
+    it = 0
+    for it in range(n_iter):
+        rows = torch.as_tensor(rs.randint(0, n, est.batch_size), dtype=torch.int64).to(sd.device)
+        reassign = None
+        if (it + 1) % (10 + int(min_count)) == 0 and est.reassignment_ratio > 0:
+            def reassign(s, rows=rows):
+                return _mb_reassign(est, s, sd, rows, rs)
+        inertia, diff, min_count = st.step(sd, xn, rows, None if sw is None else sw[rows],
+                                           reassign)
+        if est._converged(it, n_iter, tol, n, diff if tol > 0.0 else 0.0, inertia, ctx):
+            break
+    est.n_iter_ = it + 1
+    est.n_steps_ = it + 1
+    _mb_publish(est, st)
+    if est.compute_labels:
+        _mb_labels(est, sd, st, sw, xn)
+    return est
+
+
+def minibatch_partial_fit(est, X, sample_weight=None):
+    """``MiniBatchKMeans.partial_fit`` on a scipy sparse matrix: one step over
+    all rows of ``X``."""
+    sd = as_sparse_data(X, device=est.device)
+    n, d = sd.shape
+    sw = _weights(sample_weight, sd)
+    if not hasattr(est, "_rs"):
+        est._rs = check_random_state(est.random_state)
+    xn = S.sp_row_norms(sd)
+    reassign = None
+    if not hasattr(est, "_C"):
+        est._check_params(n)
+        est.n_features_in_ = d
+        counts = torch.zeros(est.n_clusters, dtype=torch.float64)
+        C = _mb_init_centers(est, X, sd, est._rs, xn)
+        est.n_steps_ = 0
+    else:
+        if d != est.n_features_in_:
+            raise ValueError(f"X has {d} features, but MiniBatchKMeans is expecting "
+                             f"{est.n_features_in_} features as input.")
+        C, counts = est._C, est._counts
+        # (a restored estimator holds its state as arrays)
+        counts = torch.as_tensor(counts)
+        if est._rs.randint(10 * (1 + int(counts.min()))) == 0 and est.reassignment_ratio > 0:
+            def reassign(s):
+                return _mb_reassign(est, s, sd, None, est._rs)
+    st = _mb_state(est, sd, sw, C, counts)
+    st.advance(sd, xn, None, sw, reassign)
+    est.n_steps_ += 1
+    _mb_publish(est, st)
+    if est.compute_labels:
+        _mb_labels(est, sd, st, sw, xn)
+    return est
+
+
+def minibatch_predict(est, X):
+    sd, C = _fitted(est, X)
+    return to_numpy(S.sp_list_estep(sd, C)[0]).astype(np.int32)
+
+
+def minibatch_score(est, X, sample_weight=None):
+    sd, C = _fitted(est, X)
+    return -float(S.sp_list_estep(sd, C, None, _weights(sample_weight, sd))[2])

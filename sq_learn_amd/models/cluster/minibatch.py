@@ -12,14 +12,20 @@ The per-step update is vectorised (one GEMM for the batch distances,
 ``index_add_`` for the per-centre sums) instead of the reference's Python
 loop over centres, so a step is a handful of device kernels; the host RNG
 (``RandomState``) draws the same batch indices as the reference.
+
+A scipy sparse matrix runs the CSR path (``_sparse.minibatch_*``, HIP kernels
+``csrc/spminibatch.hip``): the batch stays a list of row ids, the centres are
+fp64, and the host draws are those of the dense path in the same order.
 """
 
 import numpy as np
 import torch
+from scipy.sparse import issparse
 
 from ...base import BaseEstimator, ClusterMixin, TransformerMixin
 from ...runtime.device import resolve_device, to_numpy
 from ...utils.validation import check_array, check_is_fitted, check_random_state
+from . import _sparse
 from ._init import kmeans_plusplus as _kpp
 from .._data import as_data
 
@@ -147,6 +153,8 @@ class MiniBatchKMeans(TransformerMixin, ClusterMixin, BaseEstimator):
 
     # ---------------------------------------------------------------- fit
     def fit(self, X, y=None, sample_weight=None):
+        if issparse(X):
+            return _sparse.minibatch_fit(self, X, sample_weight)
         X = self._tensor(X)
         n, d = X.shape
         self._check_params(n)
@@ -186,6 +194,8 @@ class MiniBatchKMeans(TransformerMixin, ClusterMixin, BaseEstimator):
         return self
 
     def partial_fit(self, X, y=None, sample_weight=None):
+        if issparse(X):
+            return _sparse.minibatch_partial_fit(self, X, sample_weight)
         X = self._tensor(X)
         n, d = X.shape
         w = self._weights(X, sample_weight)
@@ -233,12 +243,16 @@ class MiniBatchKMeans(TransformerMixin, ClusterMixin, BaseEstimator):
 
     def predict(self, X, sample_weight=None):
         check_is_fitted(self, "cluster_centers_")
+        if issparse(X):
+            return _sparse.minibatch_predict(self, X)
         X = self._tensor(X)
         self._check_nf(X)
         return self._labels_inertia_batched(X, self._weights(X, sample_weight))[0]
 
     def transform(self, X):
         check_is_fitted(self, "cluster_centers_")
+        if issparse(X):
+            return _sparse.transform(self, X)
         X = self._tensor(X)
         self._check_nf(X)
         C = torch.as_tensor(self.cluster_centers_, device=X.device).to(X.dtype)
@@ -246,5 +260,7 @@ class MiniBatchKMeans(TransformerMixin, ClusterMixin, BaseEstimator):
         return torch.sqrt(D.clamp(min=0)).cpu().numpy()
 
     def score(self, X, y=None, sample_weight=None):
+        if issparse(X):
+            return _sparse.minibatch_score(self, X, sample_weight)
         X = self._tensor(X)
         return -self._labels_inertia_batched(X, self._weights(X, sample_weight))[1]
