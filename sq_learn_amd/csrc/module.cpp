@@ -112,6 +112,13 @@ __attribute__((weak)) int sq_spmm(const void*, const void*, const void*, const v
                                   void*, void*);
 __attribute__((weak)) int sq_sp_row_moments(const void*, const void*, void*, void*, long long,
                                             void*);
+// spknn.hip
+__attribute__((weak)) int sq_sp_knn_tile_max();
+__attribute__((weak)) int sq_sp_knn(const void*, const void*, const void*, const void*,
+                                    const void*, const void*, const void*, const void*,
+                                    const void*, long long, long long, long long, int, int,
+                                    long long, int, int, int, void*, void*, void*, void*, void*,
+                                    void*);
 // failure.hip
 __attribute__((weak)) int sq_failure_inject(void*, long long, int, double, int, unsigned, unsigned,
                                             unsigned, unsigned, unsigned, unsigned, unsigned,
@@ -572,6 +579,23 @@ static PyObject* py_spmm(PyObject*, PyObject* a) {
   return ret(rc);
 }
 
+static PyObject* py_sp_knn_tile_max(PyObject*, PyObject*) {
+  CHECK(sq_sp_knn_tile_max)
+  return PyLong_FromLong(sq_sp_knn_tile_max());
+}
+
+static PyObject* py_sp_knn(PyObject*, PyObject* a) {
+  unsigned long long qp, qi, qv, tr, tv, tab, qn, xn, qe, pd, pi, dist, od, oi, st;
+  long long q0, m, n, nnz; int d, T, kk, metric, mode;
+  if (!PyArg_ParseTuple(a, "KKKKKKKKKLLLiiLiiiKKKKKK", &qp, &qi, &qv, &tr, &tv, &tab, &qn, &xn,
+                        &qe, &q0, &m, &n, &d, &T, &nnz, &kk, &metric, &mode, &pd, &pi, &dist,
+                        &od, &oi, &st))
+    return nullptr;
+  CHECK(sq_sp_knn)
+  return ret(sq_sp_knn(P(qp), P(qi), P(qv), P(tr), P(tv), P(tab), P(qn), P(xn), P(qe), q0, m, n,
+                       d, T, nnz, kk, metric, mode, P(pd), P(pi), P(dist), P(od), P(oi), P(st)));
+}
+
 static PyObject* py_sp_row_moments(PyObject*, PyObject* a) {
   unsigned long long ip, da, sm, sq, st; long long n;
   if (!PyArg_ParseTuple(a, "KKKKLK", &ip, &da, &sm, &sq, &n, &st)) return nullptr;
@@ -886,6 +910,8 @@ static PyMethodDef methods[] = {
     {"spmm_tile_cols", py_spmm_tile_cols, METH_NOARGS, "columns per pass of the CSR x dense kernel"},
     {"spmm", py_spmm, METH_VARARGS, "CSR x dense fp64 product over row segments"},
     {"sp_row_moments", py_sp_row_moments, METH_VARARGS, "CSR per-row sum and sum of squares (fp64)"},
+    {"sp_knn_tile_max", py_sp_knn_tile_max, METH_NOARGS, "largest fit tile of the sparse k-NN kernel"},
+    {"sp_knn", py_sp_knn, METH_VARARGS, "CSR x CSR brute k-NN through an inverted index"},
     {"failure_inject", py_failure_inject, METH_VARARGS, "Bernoulli estimation failure + resampling"},
     {"tomography", py_tomography, METH_VARARGS, "batched shot-based vector tomography"},
     {"mnom_segments", py_mnom_segments, METH_VARARGS, "segmented multinomial (long vectors)"},

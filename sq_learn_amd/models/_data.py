@@ -213,6 +213,8 @@ class SparseData:
         # caches of ops/sparse_linalg.py (the sparsity structure never changes)
         self._transpose = None
         self._segments = {}
+        # tile pointer tables of ops/sparse_knn.py, by tile size
+        self._knn_tables = {}
 
     @property
     def n_local(self):

@@ -374,8 +374,21 @@ class _HostEngine:
         return (dist, ind) if return_distance else ind
 
 
+_SPARSE_RADIUS_MSG = ("radius neighbours are not supported on sparse input: the sparse "
+                      "brute-force path serves kneighbors only; densify the data (X.toarray()) "
+                      "for radius queries")
+
+
+def _refuse_sparse_radius(*arrays):
+    if any(sp.issparse(a) for a in arrays):
+        raise ValueError(_SPARSE_RADIUS_MSG)
+
+
 def _radius_neighbors(est, X=None, radius=None, return_distance=True, sort_results=False):
     check_is_fitted(est, "_X")
+    _refuse_sparse_radius(X)
+    if getattr(est, "_sp", None) is not None:
+        raise ValueError(_SPARSE_RADIUS_MSG)
     radius = est.radius if radius is None else radius
     host = getattr(est, "_host", None)
     if host is None:
@@ -405,7 +418,8 @@ class _GraphMixin:
 
     def kneighbors_graph(self, X=None, n_neighbors=None, mode="connectivity"):
         k = self.n_neighbors if n_neighbors is None else n_neighbors
-        nq = self.n_samples_fit_ if X is None else np.asarray(to_numpy(X)).shape[0]
+        nq = self.n_samples_fit_ if X is None else X.shape[0] if sp.issparse(X) \
+            else np.asarray(to_numpy(X)).shape[0]
         if mode == "connectivity":
             ind = self.kneighbors(X, k, return_distance=False)
             return _graph(nq, self.n_samples_fit_, None, np.asarray(ind), mode)
@@ -485,6 +499,7 @@ class _RadiusBase(BaseEstimator):
 
     def _fitX(self, X):
         from .knn import NearestNeighbors
+        _refuse_sparse_radius(X)
         self._nn = NearestNeighbors(radius=self.radius, algorithm=self.algorithm,
                                     leaf_size=self.leaf_size, metric=self.metric, p=self.p,
                                     metric_params=self.metric_params, device=self.device).fit(X)
@@ -634,6 +649,7 @@ class RadiusNeighborsTransformer(TransformerMixin, BaseEstimator):
 
     def fit(self, X, y=None):
         from .knn import NearestNeighbors
+        _refuse_sparse_radius(X)
         self._nn = NearestNeighbors(radius=self.radius, algorithm=self.algorithm,
                                     leaf_size=self.leaf_size, metric=self.metric, p=self.p,
                                     metric_params=self.metric_params, device=self.device).fit(X)

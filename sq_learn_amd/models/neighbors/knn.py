@@ -32,8 +32,95 @@ def _topk_rows(D, k, col_offset=0):
     return v, i + col_offset
 
 
+def _drop_self(dist, ind, k):
+    """Drop each sample itself (first occurrence of its own index) from the
+    k + 1 neighbours of a self-query."""
+    kk = ind.shape[1]
+    keep = np.ones_like(ind, dtype=bool)
+    self_pos = (ind == np.arange(ind.shape[0])[:, None])
+    first = np.where(self_pos.any(1), self_pos.argmax(1), kk - 1)
+    keep[np.arange(ind.shape[0]), first] = False
+    return dist[keep].reshape(dist.shape[0], k), ind[keep].reshape(ind.shape[0], k)
+
+
 class _NeighborsBase(BaseEstimator):
+    def _fit_sparse(self, X):
+        """Sparse rows stay CSR: euclidean / cosine brute force through
+        ``ops.sparse_knn`` (the reference resolves ``algorithm='auto'`` to
+        brute force on sparse input)."""
+        from ...models._data import as_sparse_data
+        from ...ops.sparse_kmeans import sp_row_norms
+        from ._extra import _is_euclidean
+        algo = getattr(self, "algorithm", "auto")
+        if algo in ("kd_tree", "ball_tree"):
+            raise ValueError(f"{algo} does not work with sparse matrices. Densify the data, or "
+                             "set algorithm='brute'")
+        if algo not in ("auto", "brute"):
+            raise ValueError(f"unrecognized algorithm: '{algo}'")
+        euclid = _is_euclidean(self.metric, getattr(self, "p", 2), self.metric_params)
+        if not euclid and self.metric != "cosine":
+            raise ValueError(f"Metric '{self.metric}' is not supported on sparse input: the "
+                             "sparse brute-force path computes 'euclidean' (or 'minkowski' with "
+                             "p=2) and 'cosine'; densify the data for any other metric")
+        self._sp = as_sparse_data(X, resolve_device(self.device))
+        self._sp_xn = sp_row_norms(self._sp)
+        self._X = None
+        self._host = None
+        self.n_samples_fit_, self.n_features_in_ = self._sp.shape
+        self._fit_method = "brute"
+        self.effective_metric_ = "euclidean" if euclid else self.metric
+        return self
+
+    def __getstate__(self):
+        state = super().__getstate__()
+        sd = state.get("_sp")
+        if sd is not None:
+            # host CSR arrays; caches (transpose, tile tables) are rebuilt on use
+            state["_sp"] = (sd.indptr.cpu().numpy(), sd.indices.cpu().numpy(),
+                            sd.data.cpu().numpy().astype(np.float64), sd.shape)
+        return state
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        sd = self.__dict__.get("_sp")
+        if isinstance(sd, tuple):
+            from ...models._data import SparseData
+            self._sp = SparseData(torch.as_tensor(sd[0]), torch.as_tensor(sd[1]),
+                                  torch.as_tensor(sd[2]), sd[3])
+            self._sp_xn = torch.as_tensor(self._sp_xn)
+
+    def _kneighbors_sparse(self, X, k, return_distance):
+        from ...models._data import as_sparse_data
+        from ...ops.sparse_kmeans import sp_row_norms
+        from ...ops.sparse_knn import sp_knn
+        import scipy.sparse as sp
+        fit = self._sp
+        query_is_train = X is None
+        kk = k + 1 if query_is_train else k
+        if kk > self.n_samples_fit_:
+            raise ValueError(f"Expected n_neighbors <= n_samples, but n_samples = "
+                             f"{self.n_samples_fit_}, n_neighbors = {kk}")
+        if query_is_train:
+            Q, qn = fit, self._sp_xn
+        else:
+            if not sp.issparse(X):
+                # a dense query against a sparse fit: CSR of its nonzeros
+                X = sp.csr_matrix(np.asarray(check_array(to_numpy(X)), dtype=np.float64))
+            Q = as_sparse_data(X, fit.device)
+            qn = sp_row_norms(Q)
+        D, idx = sp_knn(fit, Q, kk, metric=self.effective_metric_, xn=self._sp_xn, qn=qn)
+        if self.effective_metric_ == "euclidean":
+            D = torch.sqrt(D)
+        dist, ind = D.cpu().numpy(), idx.cpu().numpy()
+        if query_is_train:
+            dist, ind = _drop_self(dist, ind, k)
+        return (dist, ind) if return_distance else ind
+
     def _fit(self, X, y=None):
+        import scipy.sparse as sp
+        if sp.issparse(X):
+            return self._fit_sparse(X)
+        self._sp = None
         dev = resolve_device(self.device)
         if isinstance(X, torch.Tensor):
             Xt = X.to(dev)
@@ -63,10 +150,14 @@ class _NeighborsBase(BaseEstimator):
         if X is not None and np.shape(X)[-1] != self.n_features_in_:
             raise ValueError(f"X has {np.shape(X)[-1]} features, but {type(self).__name__} is "
                              f"expecting {self.n_features_in_} features as input.")
-        if getattr(self, "_host", None) is not None:
-            k = self.n_neighbors if n_neighbors is None else n_neighbors
-            return self._host.kneighbors(X, k, return_distance)
         k = self.n_neighbors if n_neighbors is None else n_neighbors
+        if getattr(self, "_sp", None) is not None:
+            return self._kneighbors_sparse(X, k, return_distance)
+        import scipy.sparse as sp
+        if sp.issparse(X):
+            X = X.toarray()      # a sparse query against a dense fit is small: densify
+        if getattr(self, "_host", None) is not None:
+            return self._host.kneighbors(X, k, return_distance)
         dev = self._X.device
         query_is_train = X is None
         Q = self._X if query_is_train else torch.as_tensor(
@@ -88,13 +179,7 @@ class _NeighborsBase(BaseEstimator):
         dist = torch.sqrt(torch.cat(dists)).cpu().numpy()
         ind = torch.cat(idxs).cpu().numpy()
         if query_is_train:
-            # drop each sample itself (first occurrence of its own index)
-            keep = np.ones_like(ind, dtype=bool)
-            self_pos = (ind == np.arange(ind.shape[0])[:, None])
-            first = np.where(self_pos.any(1), self_pos.argmax(1), kk - 1)
-            keep[np.arange(ind.shape[0]), first] = False
-            ind = ind[keep].reshape(ind.shape[0], k)
-            dist = dist[keep].reshape(dist.shape[0], k)
+            dist, ind = _drop_self(dist, ind, k)
         return (dist, ind) if return_distance else ind
 
 
@@ -112,7 +197,8 @@ class KNeighborsClassifier(ClassifierMixin, _NeighborsBase):
         self.device = device
 
     def fit(self, X, y):
-        X, y = self._validate_data(X, y) if not isinstance(X, torch.Tensor) else (X, y)
+        X, y = self._validate_data(X, y, accept_sparse=True) \
+            if not isinstance(X, torch.Tensor) else (X, y)
         self._fit(X)
         y = np.asarray(to_numpy(y))
         self.classes_, self._y = np.unique(y, return_inverse=True)
