@@ -119,6 +119,13 @@ __attribute__((weak)) int sq_sp_knn(const void*, const void*, const void*, const
                                     const void*, long long, long long, long long, int, int,
                                     long long, int, int, int, void*, void*, void*, void*, void*,
                                     void*);
+// spradius.hip
+__attribute__((weak)) int sq_sp_radius_mark(const void*, const void*, const void*, const void*,
+                                            const void*, const void*, const void*, const void*,
+                                            const void*, long long, long long, long long, int, int,
+                                            long long, int, double, int, void*, void*, void*);
+__attribute__((weak)) int sq_sp_radius_fill(const void*, const void*, long long, long long, int,
+                                            long long, void*, void*);
 // failure.hip
 __attribute__((weak)) int sq_failure_inject(void*, long long, int, double, int, unsigned, unsigned,
                                             unsigned, unsigned, unsigned, unsigned, unsigned,
@@ -596,6 +603,24 @@ static PyObject* py_sp_knn(PyObject*, PyObject* a) {
                        d, T, nnz, kk, metric, mode, P(pd), P(pi), P(dist), P(od), P(oi), P(st)));
 }
 
+static PyObject* py_sp_radius_mark(PyObject*, PyObject* a) {
+  unsigned long long qp, qi, qv, tr, tv, tab, qn, xn, qe, mask, cnt, st;
+  long long q0, m, n, nnz; int d, T, metric, self; double thr;
+  if (!PyArg_ParseTuple(a, "KKKKKKKKKLLLiiLidiKKK", &qp, &qi, &qv, &tr, &tv, &tab, &qn, &xn, &qe,
+                        &q0, &m, &n, &d, &T, &nnz, &metric, &thr, &self, &mask, &cnt, &st))
+    return nullptr;
+  CHECK(sq_sp_radius_mark)
+  return ret(sq_sp_radius_mark(P(qp), P(qi), P(qv), P(tr), P(tv), P(tab), P(qn), P(xn), P(qe), q0,
+                               m, n, d, T, nnz, metric, thr, self, P(mask), P(cnt), P(st)));
+}
+
+static PyObject* py_sp_radius_fill(PyObject*, PyObject* a) {
+  unsigned long long mask, cs, out, st; long long m, n, total; int T;
+  if (!PyArg_ParseTuple(a, "KKLLiLKK", &mask, &cs, &m, &n, &T, &total, &out, &st)) return nullptr;
+  CHECK(sq_sp_radius_fill)
+  return ret(sq_sp_radius_fill(P(mask), P(cs), m, n, T, total, P(out), P(st)));
+}
+
 static PyObject* py_sp_row_moments(PyObject*, PyObject* a) {
   unsigned long long ip, da, sm, sq, st; long long n;
   if (!PyArg_ParseTuple(a, "KKKKLK", &ip, &da, &sm, &sq, &n, &st)) return nullptr;
@@ -912,6 +937,8 @@ static PyMethodDef methods[] = {
     {"sp_row_moments", py_sp_row_moments, METH_VARARGS, "CSR per-row sum and sum of squares (fp64)"},
     {"sp_knn_tile_max", py_sp_knn_tile_max, METH_NOARGS, "largest fit tile of the sparse k-NN kernel"},
     {"sp_knn", py_sp_knn, METH_VARARGS, "CSR x CSR brute k-NN through an inverted index"},
+    {"sp_radius_mark", py_sp_radius_mark, METH_VARARGS, "CSR x CSR radius test: one bit per pair"},
+    {"sp_radius_fill", py_sp_radius_fill, METH_VARARGS, "marked pairs to ascending index lists"},
     {"failure_inject", py_failure_inject, METH_VARARGS, "Bernoulli estimation failure + resampling"},
     {"tomography", py_tomography, METH_VARARGS, "batched shot-based vector tomography"},
     {"mnom_segments", py_mnom_segments, METH_VARARGS, "segmented multinomial (long vectors)"},

@@ -7,7 +7,12 @@ each chunk, so only the CSR neighbour lists reach the host); the cluster
 expansion is the host-native depth-first pass ``sqh_dbscan_inner``
 (``csrc/host/cluster_host.cpp``).  ``metric='precomputed'`` takes a dense or
 sparse distance matrix; other metrics go through ``torch.cdist``
-(minkowski family)."""
+(minkowski family).
+
+A scipy sparse ``X`` under the euclidean or the cosine metric stays CSR: the
+neighbourhoods come from the inverted-index radius kernels
+(``ops/sparse_radius.py``, ``csrc/spradius.hip``) and ``components_`` is a
+CSR matrix.  Other metrics on sparse input are densified as before."""
 
 import numpy as np
 import scipy.sparse as sp
@@ -15,8 +20,10 @@ import torch
 
 from ...base import BaseEstimator, ClusterMixin
 from ...ops import _host
+from ...ops.sparse_radius import sp_radius
 from ...runtime.device import resolve_device, to_tensor
 from ...utils.pairwise import get_chunk_n_rows
+from .._data import as_sparse_data
 
 _P_OF = {"euclidean": 2.0, "l2": 2.0, "manhattan": 1.0, "cityblock": 1.0, "l1": 1.0,
          "chebyshev": float("inf")}
@@ -64,6 +71,23 @@ def radius_neighbors_graph(X, eps, *, metric="euclidean", p=None, device=None):
                                     np.zeros(0, dtype=np.int64))
 
 
+def _sparse_metric(metric, p):
+    """'euclidean' / 'cosine' where the CSR radius kernels serve ``metric``,
+    else None (the densifying path)."""
+    if metric in ("euclidean", "l2", "minkowski") and p in (None, 2):
+        return "euclidean"
+    return "cosine" if metric == "cosine" else None
+
+
+def sparse_radius_neighbors(X, eps, metric, device=None):
+    """CSR (indptr, indices) of the eps-neighbourhoods (self included) of the
+    rows of a scipy sparse ``X``, which is never densified.  ``metric``:
+    'euclidean' or 'cosine'."""
+    sd = as_sparse_data(X, resolve_device(device))
+    thr = eps * eps if metric == "euclidean" else eps
+    return sp_radius(sd, sd, thr, metric, include_self=True)
+
+
 def _precomputed_neighbors(X, eps):
     if sp.issparse(X):
         X = X.tocsr()
@@ -97,7 +121,14 @@ def dbscan(X, eps=0.5, *, min_samples=5, metric="minkowski", metric_params=None,
 class DBSCAN(ClusterMixin, BaseEstimator):
     """Density-based clustering (eps, min_samples, metric, ...: reference
     parameters; ``algorithm`` / ``leaf_size`` are accepted - the
-    neighbourhoods are always brute-force GEMMs on the device)."""
+    neighbourhoods are always brute force on the device).
+
+    Sparse input with ``metric`` 'euclidean' / 'l2' / 'minkowski' (p = 2) or
+    'cosine' is clustered as CSR, without a dense copy.  On a GPU the stored
+    values are held in fp32: the neighbourhoods are those of the fp32-rounded
+    rows (distances themselves are computed in fp64 from exact inner
+    products of the rounded values).  ``components_`` is then a scipy CSR
+    matrix of the caller's values."""
 
     def __init__(self, eps=0.5, *, min_samples=5, metric="euclidean", metric_params=None,
                  algorithm="auto", leaf_size=30, p=None, n_jobs=None, device=None):
@@ -118,6 +149,12 @@ class DBSCAN(ClusterMixin, BaseEstimator):
             indptr, indices = _precomputed_neighbors(X, self.eps)
             n = indptr.shape[0] - 1
             Xd = None
+        elif sp.issparse(X) and _sparse_metric(self.metric, self.p) is not None:
+            Xd = X.tocsr()
+            indptr, indices = sparse_radius_neighbors(Xd, self.eps,
+                                                      _sparse_metric(self.metric, self.p),
+                                                      self.device)
+            n = indptr.shape[0] - 1
         else:
             Xd = X if (sp.issparse(X) is False and isinstance(X, torch.Tensor)) else (
                 np.asarray(X.toarray() if sp.issparse(X) else X))
@@ -141,7 +178,9 @@ class DBSCAN(ClusterMixin, BaseEstimator):
                                          _host.ptr(labels))
         self.core_sample_indices_ = np.where(core)[0]
         self.labels_ = labels
-        if len(self.core_sample_indices_) and Xd is not None:
+        if sp.issparse(Xd):
+            self.components_ = Xd[self.core_sample_indices_]
+        elif len(self.core_sample_indices_) and Xd is not None:
             Xn = Xd.cpu().numpy() if isinstance(Xd, torch.Tensor) else Xd
             self.components_ = Xn[self.core_sample_indices_].copy()
         else:
