@@ -2,6 +2,13 @@
 // smallest distances of a distance tile produced by the library GEMM.
 // One wave per row; each lane keeps a sorted register list of its columns'
 // best KMAX, then the 64 lists are merged by kk rounds of wave-wide argmin.
+//
+// Contract: the order is (value, column) ascending, so ties go to the lower
+// column.  +inf entries are ordinary candidates (selected after every finite
+// value, with their own columns).  NaN entries are never selected: every
+// comparison with a NaN is false, so one never enters a lane's list.  A row
+// with fewer than kk candidates (kk > nref, or NaN entries) is padded with
+// (+inf, -1); col_offset is added to real columns only.
 #include "common.h"
 
 namespace sq {

@@ -120,14 +120,16 @@ __global__ void __launch_bounds__(256) mu_sums_kernel(
     const T* __restrict__ X, long long ldx, int col0, int d_total, const float* __restrict__ qs,
     int nq, float* __restrict__ rowmax, float* __restrict__ part, float* __restrict__ rowacc,
     int final, long long n, int d, long long rows_per_wg, const float* __restrict__ mean,
-    float qstep) {
+    float qstep, int base16) {
   constexpr int RPW = 64 / LPR;              // rows per wave step
   __shared__ float red[256 * 8];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int vl = lane % LPR;                  // column group of this lane
   const int sg = (wave * 64 + lane) / LPR;    // row slot within the WG (0 .. 4*RPW-1)
   const int c0 = vl * 8;
-  const bool vec = ((ldx % 8) == 0) && ((col0 % 8) == 0) && (c0 + 8 <= d);
+  // base16: X + col0 is 16-byte aligned (a column slice or an offset view of
+  // a wider buffer need not be): the 16-byte loads only then
+  const bool vec = base16 && ((ldx % 8) == 0) && ((col0 % 8) == 0) && (c0 + 8 <= d);
   const int valid = d - c0;
   // this lane's 8 column means (0 without a mean)
   float mu8[8];
@@ -303,15 +305,16 @@ __global__ void __launch_bounds__(256) mu_colsum_kernel(const float* __restrict_
 
 template <typename T>
 __global__ void __launch_bounds__(256) row_norms_kernel(const T* __restrict__ X, float* __restrict__ out,
-                                                        long long n, int d) {
-  // 16-byte vector loads; 4 rows per wave when d <= 128 elements-per-16B*16
+                                                        long long n, int d, int base16) {
+  // 16-byte vector loads (base16: X is 16-byte aligned, checked by the
+  // launcher); 4 rows per wave when d <= 128 elements-per-16B*16
   const int lane = threadIdx.x & 63;
   const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= n) return;
   constexpr int V = 16 / sizeof(T);
   const T* row = X + (size_t)r * d;
   float s = 0.f;
-  const bool aligned = ((d * sizeof(T)) % 16 == 0);
+  const bool aligned = base16 && ((d * sizeof(T)) % 16 == 0);
   if (aligned) {
     for (int c = lane * V; c < d; c += 64 * V) {
       uint4 u = *reinterpret_cast<const uint4*>(row + c);
@@ -393,16 +396,20 @@ int sq_mu_sums(const void* X, int xdtype, long long ldx, const void* qs, int nq,
     float* racc = d > 512 ? (float*)rowacc : nullptr;
     int lpr = 1;
     while (lpr * 8 < dc) lpr <<= 1;
+    const size_t esz = xdtype == 0 ? sizeof(float) : sizeof(uint16_t);
+    const int base16 = ((uintptr_t)X + (size_t)col0 * esz) % 16 == 0;
 #define MU_CASE(T, L)                                                                          \
   case L:                                                                                      \
     if (qstep > 0.f)                                                                           \
       hipLaunchKernelGGL((mu_sums_kernel<T, L, true>), dim3((unsigned)wgs), dim3(256), 0, st,  \
                          (const T*)X, ldx, col0, d, (const float*)qs, nq, (float*)rowmax,      \
-                         (float*)part, racc, final, n, dc, rpw, (const float*)mean, qstep);    \
+                         (float*)part, racc, final, n, dc, rpw, (const float*)mean, qstep,     \
+                         base16);                                                              \
     else                                                                                       \
     hipLaunchKernelGGL((mu_sums_kernel<T, L, false>), dim3((unsigned)wgs), dim3(256), 0, st,   \
                        (const T*)X, ldx, col0, d, (const float*)qs, nq, (float*)rowmax,        \
-                       (float*)part, racc, final, n, dc, rpw, (const float*)mean, qstep);      \
+                       (float*)part, racc, final, n, dc, rpw, (const float*)mean, qstep,       \
+                       base16);                                                                \
     break;
     if (xdtype == 0) {
       switch (lpr) { MU_CASE(float, 1) MU_CASE(float, 2) MU_CASE(float, 4) MU_CASE(float, 8)
@@ -447,12 +454,13 @@ int sq_row_norms(const void* X, int xdtype, void* out, long long n, int d, void*
   if (n <= 0) return 0;
   unsigned grid = (unsigned)((n + 3) / 4);
   hipStream_t st = (hipStream_t)stream;
+  const int base16 = (uintptr_t)X % 16 == 0;
   if (xdtype == 0)
     hipLaunchKernelGGL(row_norms_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)X,
-                       (float*)out, n, d);
+                       (float*)out, n, d, base16);
   else if (xdtype == 2)
     hipLaunchKernelGGL(row_norms_kernel<uint16_t>, dim3(grid), dim3(256), 0, st,
-                       (const uint16_t*)X, (float*)out, n, d);
+                       (const uint16_t*)X, (float*)out, n, d, base16);
   else
     return (int)hipErrorInvalidValue;
   return (int)hipGetLastError();

@@ -32,6 +32,38 @@ def _topk_rows(D, k, col_offset=0):
     return v, i + col_offset
 
 
+# Query rows per library GEMM call on the device.  The BLAS picks its kernel,
+# and with it the summation order, by the shape of the product: an 8-row
+# tile of q @ X.T differs from the same rows of a 40-row tile in most entries
+# at d = 61 (one fp32 ulp).  So the products are always formed in slabs of
+# _gemm_rows(n_fit) query rows at row offsets that are multiples of it (only
+# the query's last slab is shorter), and a distance tile is a whole number
+# of slabs: every GEMM call is then the same call whatever
+# ``working_memory`` is, and ``kneighbors`` returns the same bits for every
+# tile size.  A query of at most one slab is the one GEMM it was before.
+# The slab height depends on the fitted set alone: 1024 rows while such a
+# slab of products stays within 256 MiB, down to 128 for larger sets.
+# Measured against one GEMM per tile (queries x fit x d): 7000 x 63000 x 61
+# 5.98 -> 6.08 ms, 10000 x 60000 x 784 14.77 -> 14.95 ms, 2000 x 1M x 64
+# 82.3 -> 82.2 ms, 5000 x 5000 x 32 (launch-bound) 0.38 -> 0.43 ms; slabs of
+# 128 rows there cost 1.09 ms, hence the larger slab for small fitted sets.
+_SLAB_BYTES = 256 << 20
+
+
+def _gemm_rows(n_fit):
+    fit = _SLAB_BYTES // (4 * max(int(n_fit), 1))
+    return 1 << max(7, min(10, fit.bit_length() - 1))
+
+
+def _slab_products(Q, X, s, e, B):
+    """Rows s:e of Q @ X.T (s a multiple of the slab height B), slab by slab."""
+    G = torch.empty((e - s, X.shape[0]), dtype=Q.dtype, device=Q.device)
+    XT = X.T
+    for b in range(s, e, B):
+        torch.mm(Q[b:min(b + B, e)], XT, out=G[b - s:min(b + B, e) - s])
+    return G
+
+
 def _drop_self(dist, ind, k):
     """Drop each sample itself (first occurrence of its own index) from the
     k + 1 neighbours of a self-query."""
@@ -167,10 +199,22 @@ class _NeighborsBase(BaseEstimator):
             raise ValueError(f"Expected n_neighbors <= n_samples, but n_samples = "
                              f"{self.n_samples_fit_}, n_neighbors = {kk}")
         rows = get_chunk_n_rows(4 * self.n_samples_fit_)
+        slabs = nat.use_native(Q)
+        if slabs:
+            # whole slabs per tile (at least one: working_memory is honoured
+            # in units of one slab of query rows); the norms once for all rows
+            B = _gemm_rows(self.n_samples_fit_)
+            rows = max(B, rows // B * B)
+            qn = (Q * Q).sum(1)
         dists, idxs = [], []
         for s in range(0, Q.shape[0], rows):
             q = Q[s:s + rows]
-            D = ((q * q).sum(1)[:, None] + self._xn[None, :] - 2.0 * (q @ self._X.T)).clamp_(min=0)
+            if slabs:
+                D = (qn[s:s + rows, None] + self._xn[None, :]
+                     - 2.0 * _slab_products(Q, self._X, s, s + q.shape[0], B)).clamp_(min=0)
+            else:
+                D = ((q * q).sum(1)[:, None] + self._xn[None, :]
+                     - 2.0 * (q @ self._X.T)).clamp_(min=0)
             if D.dtype != torch.float32 and nat.use_native(D):
                 D = D.float()
             v, i = _topk_rows(D, kk)

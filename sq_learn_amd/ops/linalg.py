@@ -233,6 +233,8 @@ def col_moments_local(X):
     of X."""
     n, d = X.shape
     if nat.use_native(X) and X.dtype in (torch.float32, torch.bfloat16) and n > 0:
+        if X.stride(1) != 1:    # the kernel takes a row stride only
+            X = X.contiguous()
         # the launcher's own partition (sq_col_moments): every one of its
         # wgs blocks writes its row of partials, so no zero-fill and no rows
         # beyond the ones used (ADVICE r4: 2048 x 2d was ~2 GiB at d = 65k)
