@@ -16,33 +16,16 @@
 //     (the first 64 nonzeros stay in registers).  Distances
 //     D_j = max(xn + cn_j - 2 acc_j, 0) go to a per-wave LDS row of k doubles
 //     (band mode) or straight to global memory (gram / sqdist modes).
-//   M-step (sp_mstep_kernel): w_i * v quantised to 64-bit integer quanta of
-//     2^xexp and added with 64-bit integer vector atomics into a k x d int64
-//     buffer; integer addition commutes, so the sums do not depend on the
-//     arrival order or the launch geometry.  sp_mstep_finish converts to fp64.
+//   M-step (sp_mstep_kernel of sp_rows.h): w_i * v quantised to 64-bit
+//     integer quanta of 2^xexp and added with 64-bit integer vector atomics
+//     into a k x d int64 buffer; integer addition commutes, so the sums do not
+//     depend on the arrival order or the launch geometry.  sp_mstep_finish
+//     converts to fp64.
+//   Row norms: sp_row_moments_kernel of sp_rows.h without the sum.
 #include "band.h"
 #include "sp_rows.h"
 
 namespace sq {
-
-// ------------------------------------------------------------- row norms
-__global__ void __launch_bounds__(256) sp_row_norms_kernel(
-    const long long* __restrict__ indptr, const float* __restrict__ data,
-    double* __restrict__ xn, long long n) {
-  const int lane = threadIdx.x & 63;
-  const int wpb = blockDim.x >> 6;
-  const long long stride = (long long)gridDim.x * wpb;
-  for (long long i = (long long)blockIdx.x * wpb + (threadIdx.x >> 6); i < n; i += stride) {
-    const long long s = indptr[i], e = indptr[i + 1];
-    double acc = 0.0;
-    for (long long p = s + lane; p < e; p += 64) {
-      const double v = (double)data[p];
-      acc += v * v;
-    }
-    acc = wave_sum(acc);
-    if (lane == 0) xn[i] = acc;
-  }
-}
 
 // ---------------------------------------------------------------- E-step
 // mode 0: band (labels, mind, per-wave inertia partials)
@@ -64,44 +47,19 @@ __global__ void __launch_bounds__(256) sp_estep_kernel(
   double inertia = 0.0;
   for (long long i = row0 + (long long)blockIdx.x * wpb + wave; i < row1; i += stride) {
     // wave-uniform row extent in scalar registers
-    const long long s = ((long long)__builtin_amdgcn_readfirstlane((int)(indptr[i] >> 32)) << 32) |
-                        (unsigned)__builtin_amdgcn_readfirstlane((int)indptr[i]);
-    const long long e = ((long long)__builtin_amdgcn_readfirstlane((int)(indptr[i + 1] >> 32)) << 32) |
-                        (unsigned)__builtin_amdgcn_readfirstlane((int)indptr[i + 1]);
+    const long long s = sp_uniform_ll(indptr[i]);
+    const long long e = sp_uniform_ll(indptr[i + 1]);
     const double xi = xn[i];
     // the first 64 nonzeros stay in registers across the centroid tiles
-    int col0 = 0;
-    float v0 = 0.0f;
-    if (s + lane < e) {
-      col0 = indices[s + lane];
-      v0 = data[s + lane];
-    }
-    const int cnt0 = (int)((e - s) < 64 ? (e - s) : 64);
+    int col0;
+    float v0;
+    const int cnt0 = sp_load_pairs(indices, data, s, e, lane, col0, v0);
     double mn = INFINITY;
     for (int j0 = 0; j0 < k_pad; j0 += 64 * SP_T) {
-      double acc[SP_T];
-#pragma unroll
-      for (int t = 0; t < SP_T; ++t) acc[t] = 0.0;
+      SpAcc acc = 0.0;
       const int nt = (k_pad - j0) >= 64 * SP_T ? SP_T : (k_pad - j0) / 64;   // wave-uniform
-      const double* CTj = CT + j0 + lane;
-      long long p = s;
-      int col = col0, cnt = cnt0;
-      float v = v0;
-      while (true) {
-        if (nt == SP_T) sp_accumulate<SP_T>(acc, CTj, k_pad, col, v, cnt);
-        else if (nt == 3) sp_accumulate<3>(acc, CTj, k_pad, col, v, cnt);
-        else if (nt == 2) sp_accumulate<2>(acc, CTj, k_pad, col, v, cnt);
-        else sp_accumulate<1>(acc, CTj, k_pad, col, v, cnt);
-        p += 64;
-        if (p >= e) break;
-        col = 0;
-        v = 0.0f;
-        if (p + lane < e) {
-          col = indices[p + lane];
-          v = data[p + lane];
-        }
-        cnt = (int)((e - p) < 64 ? (e - p) : 64);
-      }
+      sp_walk<true>(acc, nt, CT + j0 + lane, k_pad, SpPadded(), indices, data, s, e, lane, col0,
+                    v0, cnt0);
 #pragma unroll
       for (int t = 0; t < SP_T; ++t) {
         const int j = j0 + lane + 64 * t;
@@ -139,32 +97,6 @@ __global__ void __launch_bounds__(256) sp_estep_kernel(
 }
 
 // ---------------------------------------------------------------- M-step
-__global__ void __launch_bounds__(256) sp_mstep_kernel(
-    const long long* __restrict__ indptr, const int* __restrict__ indices,
-    const float* __restrict__ data, const int* __restrict__ labels,
-    const double* __restrict__ weights, long long n, int d, int k, double xscale, double wscale,
-    long long* __restrict__ qsum, long long* __restrict__ qcnt) {
-  const int lane = threadIdx.x & 63;
-  const int wpb = blockDim.x >> 6;
-  const long long stride = (long long)gridDim.x * wpb;
-  for (long long i = (long long)blockIdx.x * wpb + (threadIdx.x >> 6); i < n; i += stride) {
-    const int lab = labels[i];
-    if (lab < 0 || lab >= k) continue;
-    const double w = weights ? weights[i] : 1.0;
-    const long long s = indptr[i], e = indptr[i + 1];
-    long long* row = qsum + (long long)lab * d;
-    for (long long p = s + lane; p < e; p += 64) {
-      const int c = indices[p];
-      const long long q = __double2ll_rn(w * (double)data[p] * xscale);
-      if (q != 0 && c >= 0 && c < d)
-        atomicAdd(reinterpret_cast<unsigned long long*>(row + c), (unsigned long long)q);
-    }
-    if (lane == 0)
-      atomicAdd(reinterpret_cast<unsigned long long*>(qcnt + lab),
-                (unsigned long long)__double2ll_rn(w * wscale));
-  }
-}
-
 __global__ void __launch_bounds__(256) sp_mstep_finish_kernel(
     const long long* __restrict__ qsum, const long long* __restrict__ qcnt, long long kd, int k,
     double xq, double wq, double* __restrict__ sums, double* __restrict__ counts) {
@@ -182,8 +114,9 @@ using namespace sq;
 extern "C" int sq_sp_row_norms(const void* indptr, const void* data, void* xn, long long n,
                                void* stream) {
   if (n <= 0) return 0;
-  hipLaunchKernelGGL(sp_row_norms_kernel, dim3(sp_grid(n, 4)), dim3(256), 0, (hipStream_t)stream,
-                     (const long long*)indptr, (const float*)data, (double*)xn, n);
+  hipLaunchKernelGGL(sp_row_moments_kernel<false>, dim3(sp_grid(n, 4)), dim3(256), 0,
+                     (hipStream_t)stream, (const long long*)indptr, (const float*)data,
+                     (double*)nullptr, (double*)xn, n);
   return (int)hipGetLastError();
 }
 
@@ -249,10 +182,11 @@ extern "C" int sq_sp_mstep(const void* indptr, const void* indices, const void* 
   if (k < 1 || d < 1) return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
   if (n > 0) {
-    hipLaunchKernelGGL(sp_mstep_kernel, dim3(sp_grid(n, 4)), dim3(256), 0, s,
+    hipLaunchKernelGGL(sp_mstep_kernel<false>, dim3(sp_grid(n, 4)), dim3(256), 0, s,
                        (const long long*)indptr, (const int*)indices, (const float*)data,
-                       (const int*)labels, (const double*)weights, n, d, k, ldexp(1.0, -xexp),
-                       ldexp(1.0, -wexp), (long long*)qsum, (long long*)qcnt);
+                       (const long long*)nullptr, 0LL, (const int*)labels, (const double*)weights,
+                       n, n, d, k, ldexp(1.0, -xexp), ldexp(1.0, -wexp), (long long*)qsum,
+                       (long long*)qcnt);
     int rc = (int)hipGetLastError();
     if (rc != 0) return rc;
   }

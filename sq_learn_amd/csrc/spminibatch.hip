@@ -6,12 +6,12 @@
 // replacement; nothing is copied or densified per step.
 //
 // MI355X mapping.
-//   sp_list_estep_kernel: one wave per list position, the gather scheme of
-//     sp_estep_kernel (sp_rows.h) against CT[d][k_pad]; the label is the plain
-//     argmin (lowest index on exact ties), kept in registers and reduced
-//     across the wave - no LDS row, always 4 waves per workgroup.
-//   sp_list_mstep_kernel: sp_mstep_kernel over the list, 64-bit integer
-//     vector atomics into the k x d quanta.
+//   sp_list_estep_kernel: one wave per list position, the tile walk of
+//     sp_estep_kernel (sp_walk of sp_rows.h) against CT[d][k_pad]; the label
+//     is the plain argmin (lowest index on exact ties), kept in registers and
+//     reduced across the wave - no LDS row, always 4 waves per workgroup.
+//   Scatter: sp_mstep_kernel of sp_rows.h over the list, with the rule that a
+//     position of zero weight quantum adds nothing.
 //   mb_update_kernel: one pass over the dense k x d state in 64 x 64 tiles:
 //     c' = (c n_c + sum) / (n_c + w_c) for the centres the batch touched,
 //     written to C (rows along features) and, through an LDS tile transpose,
@@ -51,39 +51,16 @@ __global__ void __launch_bounds__(256) sp_list_estep_kernel(
     const long long e = sp_uniform_ll(indptr[i + 1]);
     const double xi = xn[i];
     // the first 64 nonzeros stay in registers across the centroid tiles
-    int col0 = 0;
-    float v0 = 0.0f;
-    if (s + lane < e) {
-      col0 = indices[s + lane];
-      v0 = data[s + lane];
-    }
-    const int cnt0 = (int)((e - s) < 64 ? (e - s) : 64);
+    int col0;
+    float v0;
+    const int cnt0 = sp_load_pairs(indices, data, s, e, lane, col0, v0);
     double bd = INFINITY;
     int bj = 0x7fffffff;
     for (int j0 = 0; j0 < k_pad; j0 += 64 * SP_T) {
-      double acc[SP_T];
-#pragma unroll
-      for (int t = 0; t < SP_T; ++t) acc[t] = 0.0;
+      SpAcc acc = 0.0;
       const int nt = (k_pad - j0) >= 64 * SP_T ? SP_T : (k_pad - j0) / 64;   // wave-uniform
-      const double* CTj = CT + j0 + lane;
-      long long p = s;
-      int col = col0, cnt = cnt0;
-      float v = v0;
-      while (true) {
-        if (nt == SP_T) sp_accumulate<SP_T>(acc, CTj, k_pad, col, v, cnt);
-        else if (nt == 3) sp_accumulate<3>(acc, CTj, k_pad, col, v, cnt);
-        else if (nt == 2) sp_accumulate<2>(acc, CTj, k_pad, col, v, cnt);
-        else sp_accumulate<1>(acc, CTj, k_pad, col, v, cnt);
-        p += 64;
-        if (p >= e) break;
-        col = 0;
-        v = 0.0f;
-        if (p + lane < e) {
-          col = indices[p + lane];
-          v = data[p + lane];
-        }
-        cnt = (int)((e - p) < 64 ? (e - p) : 64);
-      }
+      sp_walk<true>(acc, nt, CT + j0 + lane, k_pad, SpPadded(), indices, data, s, e, lane, col0,
+                    v0, cnt0);
       // a lane meets its centroids in increasing j: strict < keeps the lowest
 #pragma unroll
       for (int t = 0; t < SP_T; ++t) {
@@ -114,38 +91,6 @@ __global__ void __launch_bounds__(256) sp_list_estep_kernel(
     inertia += (weights ? weights[pos] : 1.0) * bd;
   }
   if (lane == 0) part[(long long)blockIdx.x * wpb + wave] = inertia;
-}
-
-// ---------------------------------------------------------------- scatter
-// A position whose weight quantum rounds to zero adds nothing at all, so a
-// centre with a zero weight sum has an all-zero row of quanta.
-__global__ void __launch_bounds__(256) sp_list_mstep_kernel(
-    const long long* __restrict__ indptr, const int* __restrict__ indices,
-    const float* __restrict__ data, const long long* __restrict__ rows, long long row0,
-    const int* __restrict__ labels, const double* __restrict__ weights, long long m, long long n,
-    int d, int k, double xscale, double wscale, long long* __restrict__ qsum,
-    long long* __restrict__ qcnt) {
-  const int lane = threadIdx.x & 63;
-  const int wpb = blockDim.x >> 6;
-  const long long stride = (long long)gridDim.x * wpb;
-  for (long long pos = (long long)blockIdx.x * wpb + (threadIdx.x >> 6); pos < m; pos += stride) {
-    const long long i = rows ? rows[pos] : row0 + pos;
-    const int lab = labels[pos];
-    if (i < 0 || i >= n || lab < 0 || lab >= k) continue;
-    const double w = weights ? weights[pos] : 1.0;
-    const long long qw = __double2ll_rn(w * wscale);
-    if (qw == 0) continue;
-    const long long s = indptr[i], e = indptr[i + 1];
-    long long* row = qsum + (long long)lab * d;
-    for (long long p = s + lane; p < e; p += 64) {
-      const int c = indices[p];
-      const long long q = __double2ll_rn(w * (double)data[p] * xscale);
-      if (q != 0 && c >= 0 && c < d)
-        atomicAdd(reinterpret_cast<unsigned long long*>(row + c), (unsigned long long)q);
-    }
-    if (lane == 0)
-      atomicAdd(reinterpret_cast<unsigned long long*>(qcnt + lab), (unsigned long long)qw);
-  }
 }
 
 // ---------------------------------------------------------------- update
@@ -342,7 +287,7 @@ extern "C" int sq_sp_list_mstep(const void* indptr, const void* indices, const v
   if (k < 1 || d < 1 || m < 0) return (int)hipErrorInvalidValue;
   if (!rows && (row0 < 0 || row0 + m > n)) return (int)hipErrorInvalidValue;
   if (m == 0) return 0;
-  hipLaunchKernelGGL(sp_list_mstep_kernel, dim3(sp_grid(m, 4)), dim3(256), 0,
+  hipLaunchKernelGGL(sp_mstep_kernel<true>, dim3(sp_grid(m, 4)), dim3(256), 0,
                      (hipStream_t)stream, (const long long*)indptr, (const int*)indices,
                      (const float*)data, (const long long*)rows, row0, (const int*)labels,
                      (const double*)weights, m, n, d, k, ldexp(1.0, -xexp), ldexp(1.0, -wexp),

@@ -81,7 +81,7 @@ class _NeighborsBase(BaseEstimator):
         ``ops.sparse_knn`` (the reference resolves ``algorithm='auto'`` to
         brute force on sparse input)."""
         from ...models._data import as_sparse_data
-        from ...ops.sparse_kmeans import sp_row_norms
+        from ...ops._csr import sp_row_norms
         from ._extra import _is_euclidean
         algo = getattr(self, "algorithm", "auto")
         if algo in ("kd_tree", "ball_tree"):
@@ -123,7 +123,7 @@ class _NeighborsBase(BaseEstimator):
 
     def _kneighbors_sparse(self, X, k, return_distance):
         from ...models._data import as_sparse_data
-        from ...ops.sparse_kmeans import sp_row_norms
+        from ...ops._csr import sp_row_norms
         from ...ops.sparse_knn import sp_knn
         import scipy.sparse as sp
         fit = self._sp

@@ -23,20 +23,11 @@ import torch
 
 from . import _native as nat
 from . import kmeans as K
+from ._csr import (TWIN_CHUNK, chunks, csr_ptrs, native_ok, row_list, sp_row_norms,  # noqa: F401
+                   sp_row_norms_torch)
 
 MAX_K = 16384          # LDS row of k doubles: 128 KiB at one wave per workgroup
-TWIN_CHUNK = 2048      # rows densified at a time by the torch twins
 _PARTS = 8192          # per-wave inertia partials of the persistent grid
-
-
-def _native_ok(sd):
-    if not nat.use_native(sd.data):
-        return False
-    if sd.data.dtype != torch.float32 or sd.indices.dtype != torch.int32 \
-            or sd.indptr.dtype != torch.int64:
-        raise TypeError("native sparse ops take fp32 values, int32 indices and int64 indptr")
-    nat.native()   # raises when the HIP layer is unavailable: no silent fallback
-    return True
 
 
 def check_k(k):
@@ -54,43 +45,47 @@ def center_operand(C):
     return CT, (Cd * Cd).sum(1).contiguous()
 
 
-def _chunks(n, step):
-    for s in range(0, n, step):
-        yield s, min(n, s + step)
-
-
-# ------------------------------------------------------------- row norms
-def sp_row_norms(sd):
-    """Squared row norms (fp64, n)."""
-    n = sd.shape[0]
-    if _native_ok(sd):
-        xn = torch.empty(n, dtype=torch.float64, device=sd.device)
-        nat.native().sp_row_norms(sd.indptr.data_ptr(), sd.data.data_ptr(), xn.data_ptr(), n,
-                                  nat.stream_handle(sd.device))
-        return xn
-    return sp_row_norms_torch(sd)
-
-
-def sp_row_norms_torch(sd):
-    xn = torch.zeros(sd.shape[0], dtype=torch.float64, device=sd.device)
-    if sd.nnz:
-        v = sd.data.double()
-        xn.index_add_(0, sd.row_ids(), v * v)
-    return xn
-
-
 # ---------------------------------------------------------------- E-step
+def _operand(sd, C, operand, xn):
+    """(CT, cn, xn) of a native E-step-family launch: the caller's
+    ``operand`` or ``center_operand(C)``, checked against the matrix.
+    ``xn=None`` (the gram mode does not use the norms) stands for a cached
+    zero vector."""
+    k = C.shape[0]
+    check_k(k)
+    CT, cn = operand if operand is not None else center_operand(C)
+    if xn is None:
+        xn = getattr(sd, "_zero_norms", None)
+        if xn is None:
+            xn = sd._zero_norms = torch.zeros(sd.shape[0], dtype=torch.float64, device=sd.device)
+    assert CT.dtype == torch.float64 and CT.is_contiguous() and CT.shape[0] == sd.shape[1]
+    assert cn.dtype == torch.float64 and cn.numel() >= k
+    assert xn.dtype == torch.float64 and xn.numel() >= sd.shape[0]
+    return CT, cn, xn
+
+
 def _launch(sd, CT, cn, xn, r0, r1, k, mode, delta, key, row_offset, labels, mind, part, inertia,
             out, ldo):
-    assert CT.dtype == torch.float64 and CT.is_contiguous() and CT.shape[0] == sd.shape[1]
-    assert cn.dtype == torch.float64 and cn.numel() >= k and xn.dtype == torch.float64
-    assert 0 <= r0 <= r1 <= sd.shape[0] and xn.numel() >= sd.shape[0]
+    assert 0 <= r0 <= r1 <= sd.shape[0]
     k0, k1, s0, s1 = key.as_tuple() if key is not None else (0, 0, 0, 0)
-    nat.native().sp_estep(sd.indptr.data_ptr(), sd.indices.data_ptr(), sd.data.data_ptr(),
-                          CT.data_ptr(), cn.data_ptr(), xn.data_ptr(), int(r0), int(r1),
-                          sd.shape[1], int(k), CT.shape[1], int(mode), float(delta), k0, k1, s0,
-                          s1, int(row_offset), nat.ptr(labels), nat.ptr(mind), nat.ptr(part),
-                          nat.ptr(inertia), nat.ptr(out), int(ldo), nat.stream_handle(sd.device))
+    nat.native().sp_estep(*csr_ptrs(sd), CT.data_ptr(), cn.data_ptr(), xn.data_ptr(), int(r0),
+                          int(r1), sd.shape[1], int(k), CT.shape[1], int(mode), float(delta), k0,
+                          k1, s0, s1, int(row_offset), nat.ptr(labels), nat.ptr(mind),
+                          nat.ptr(part), nat.ptr(inertia), nat.ptr(out), int(ldo),
+                          nat.stream_handle(sd.device))
+
+
+def _launch_rows(sd, C, s, e, xn, out, operand, mode, dtype):
+    """The gram (mode 1, fp32) or sqdist (mode 2, fp64) block of rows [s, e)."""
+    k = C.shape[0]
+    CT, cn, xn = _operand(sd, C, operand, xn)
+    if out is None:
+        out = torch.empty((e - s, k), dtype=dtype, device=sd.device)
+    assert out.dtype == dtype and out.stride(1) == 1 and out.shape[0] >= e - s \
+        and out.shape[1] >= k
+    _launch(sd, CT, cn, xn, s, e, k, mode, 0.0, None, 0, None, None, None, None, out,
+            out.stride(0))
+    return out[:e - s, :k]
 
 
 def sp_estep(sd, C, delta, key, row_offset=0, xn=None, operand=None):
@@ -98,19 +93,17 @@ def sp_estep(sd, C, delta, key, row_offset=0, xn=None, operand=None):
     (labels int32 on GPU / int64 on CPU, mind fp64 - the row minimum,
     inertia fp64 [1])."""
     n = sd.shape[0]
-    k = C.shape[0]
     if xn is None:
         xn = sp_row_norms(sd)
-    if _native_ok(sd):
-        check_k(k)
-        CT, cn = operand if operand is not None else center_operand(C)
+    if native_ok(sd):
+        CT, cn, xn = _operand(sd, C, operand, xn)
         dev = sd.device
         labels = torch.empty(n, dtype=torch.int32, device=dev)
         mind = torch.empty(n, dtype=torch.float64, device=dev)
         part = torch.zeros(_PARTS, dtype=torch.float64, device=dev)
         inertia = torch.zeros(1, dtype=torch.float64, device=dev)
-        _launch(sd, CT, cn, xn, 0, n, k, 0, delta, key, row_offset, labels, mind, part, inertia,
-                None, 0)
+        _launch(sd, CT, cn, xn, 0, n, C.shape[0], 0, delta, key, row_offset, labels, mind, part,
+                inertia, None, 0)
         return labels, mind, inertia
     return sp_estep_torch(sd, C, delta, key, row_offset, xn=xn)
 
@@ -124,7 +117,7 @@ def sp_estep_torch(sd, C, delta, key, row_offset=0, xn=None, chunk_rows=TWIN_CHU
         xn = sp_row_norms_torch(sd)
     labels = torch.empty(n, dtype=torch.int64, device=sd.device)
     mind = torch.empty(n, dtype=torch.float64, device=sd.device)
-    for s, e in _chunks(n, chunk_rows):
+    for s, e in chunks(n, chunk_rows):
         D = K.distances_torch(sd.dense_rows(s, e), Cd, xn[s:e].double(), cn)
         g = torch.arange(s, e, dtype=torch.int64, device=sd.device) + row_offset
         labels[s:e], mind[s:e] = K.band_select_torch(D, g, delta, key, k_pad)
@@ -137,30 +130,13 @@ def sp_gram(sd, C, rows=None, out=None, operand=None):
     n = sd.shape[0]
     s, e, _ = (rows if rows is not None else slice(None)).indices(n)
     k = C.shape[0]
-    if _native_ok(sd):
-        check_k(k)
-        CT, cn = operand if operand is not None else center_operand(C)
-        if out is None:
-            out = torch.empty((e - s, k), dtype=torch.float32, device=sd.device)
-        assert out.dtype == torch.float32 and out.stride(1) == 1 and out.shape[0] >= e - s \
-            and out.shape[1] >= k
-        _launch_rows(sd, CT, cn, None, s, e, k, 1, out)
-        return out[:e - s, :k]
+    if native_ok(sd):
+        return _launch_rows(sd, C, s, e, None, out, operand, 1, torch.float32)
     G = torch.empty((e - s, k), dtype=torch.float64, device=sd.device) if out is None else out
     Cd = C.double()
-    for a, b in _chunks(e - s, TWIN_CHUNK):
+    for a, b in chunks(e - s, TWIN_CHUNK):
         G[a:b, :k] = (sd.dense_rows(s + a, s + b) @ Cd.T).to(G.dtype)
     return G[:e - s, :k]
-
-
-def _launch_rows(sd, CT, cn, xn, s, e, k, mode, out):
-    if xn is None:
-        # the gram mode does not use the norms
-        xn = getattr(sd, "_zero_norms", None)
-        if xn is None:
-            xn = sd._zero_norms = torch.zeros(sd.shape[0], dtype=torch.float64, device=sd.device)
-    _launch(sd, CT, cn, xn, s, e, k, mode, 0.0, None, 0, None, None, None, None, out,
-            out.stride(0))
 
 
 def sp_sqdist(sd, C, rows=None, xn=None, out=None, operand=None):
@@ -170,19 +146,12 @@ def sp_sqdist(sd, C, rows=None, xn=None, out=None, operand=None):
     k = C.shape[0]
     if xn is None:
         xn = sp_row_norms(sd)
-    if _native_ok(sd):
-        check_k(k)
-        CT, cn = operand if operand is not None else center_operand(C)
-        if out is None:
-            out = torch.empty((e - s, k), dtype=torch.float64, device=sd.device)
-        assert out.dtype == torch.float64 and out.stride(1) == 1 and out.shape[0] >= e - s \
-            and out.shape[1] >= k
-        _launch_rows(sd, CT, cn, xn, s, e, k, 2, out)
-        return out[:e - s, :k]
+    if native_ok(sd):
+        return _launch_rows(sd, C, s, e, xn, out, operand, 2, torch.float64)
     D = torch.empty((e - s, k), dtype=torch.float64, device=sd.device) if out is None else out
     Cd = C.double()
     cn = (Cd * Cd).sum(1)
-    for a, b in _chunks(e - s, TWIN_CHUNK):
+    for a, b in chunks(e - s, TWIN_CHUNK):
         D[a:b, :k] = K.distances_torch(sd.dense_rows(s + a, s + b), Cd,
                                        xn[s + a:s + b].double(), cn)
     return D[:e - s, :k]
@@ -220,7 +189,7 @@ class SparseReduce:
 
 def sp_centroid_sums(sd, labels, k, weights=None, ws=None):
     """sums[l] = sum_{i: label_i = l} w_i x_i (fp64 [k, d]) and counts[l] = sum w_i."""
-    if _native_ok(sd):
+    if native_ok(sd):
         n, d = sd.shape
         if ws is None:
             ws = SparseReduce(sd, k, weights)
@@ -229,10 +198,9 @@ def sp_centroid_sums(sd, labels, k, weights=None, ws=None):
         sums = torch.empty((k, d), dtype=torch.float64, device=sd.device)
         counts = torch.empty(k, dtype=torch.float64, device=sd.device)
         ws.q.zero_()
-        nat.native().sp_mstep(sd.indptr.data_ptr(), sd.indices.data_ptr(), sd.data.data_ptr(),
-                              lab.contiguous().data_ptr(), nat.ptr(w), n, d, int(k), ws.xexp,
-                              ws.wexp, ws.q.data_ptr(), ws.q[k * d:].data_ptr(), sums.data_ptr(),
-                              counts.data_ptr(), nat.stream_handle(sd.device))
+        nat.native().sp_mstep(*csr_ptrs(sd), lab.contiguous().data_ptr(), nat.ptr(w), n, d,
+                              int(k), ws.xexp, ws.wexp, ws.q.data_ptr(), ws.q[k * d:].data_ptr(),
+                              sums.data_ptr(), counts.data_ptr(), nat.stream_handle(sd.device))
         return sums, counts
     return sp_centroid_sums_torch(sd, labels, k, weights)
 
@@ -241,7 +209,7 @@ def sp_centroid_sums_torch(sd, labels, k, weights=None, chunk_rows=TWIN_CHUNK):
     n, d = sd.shape
     sums = torch.zeros((k, d), dtype=torch.float64, device=sd.device)
     counts = torch.zeros(k, dtype=torch.float64, device=sd.device)
-    for s, e in _chunks(n, chunk_rows):
+    for s, e in chunks(n, chunk_rows):
         sm, ct = K.centroid_sums_torch(sd.dense_rows(s, e), labels[s:e], k,
                                        None if weights is None else weights[s:e],
                                        acc_dtype=torch.float64)
@@ -253,17 +221,8 @@ def sp_centroid_sums_torch(sd, labels, k, weights=None, chunk_rows=TWIN_CHUNK):
 # ------------------------------------------------------------- row lists
 # (csrc/spminibatch.hip): a mini-batch is a list of CSR row ids drawn with
 # replacement; ``rows=None`` means the contiguous rows [0, n).
-def _row_list(sd, rows):
-    if rows is None:
-        return None
-    rows = torch.as_tensor(rows, dtype=torch.int64)
-    if rows.device != sd.device:
-        rows = rows.to(sd.device)          # the batch ids go up in one copy
-    return rows.contiguous()
-
-
 def sp_rows_dense_torch(sd, rows, out=None, dst=None):
-    rows = _row_list(sd, rows)
+    rows = row_list(sd, rows)
     m, d = rows.numel(), sd.d
     if out is None:
         out = torch.zeros((m, d), dtype=torch.float64, device=sd.device)
@@ -289,26 +248,26 @@ def sp_rows_dense(sd, rows, out=None, dst=None):
     """CSR rows ``rows`` (any order, repeats allowed) as dense fp64 rows:
     ``out[t] = X[rows[t]]``, or ``out[dst[t]] = X[rows[t]]`` (the reference's
     ``assign_rows_csr``) with distinct ``dst``.  ``out`` must be contiguous."""
-    rows = _row_list(sd, rows)
+    rows = row_list(sd, rows)
     m = rows.numel()
     if dst is not None:
-        dst = _row_list(sd, dst)
+        dst = row_list(sd, dst)
         assert out is not None and dst.numel() == m
     if out is not None:
         assert out.dtype == torch.float64 and out.is_contiguous() and out.shape[1] == sd.d
-    if not _native_ok(sd):
+    if not native_ok(sd):
         return sp_rows_dense_torch(sd, rows, out, dst)
     if out is None:
         out = torch.empty((m, sd.d), dtype=torch.float64, device=sd.device)
-    nat.native().sp_rows_dense(sd.indptr.data_ptr(), sd.indices.data_ptr(), sd.data.data_ptr(),
-                               rows.data_ptr(), nat.ptr(dst), m, sd.shape[0], out.shape[0], sd.d,
-                               out.data_ptr(), out.stride(0), nat.stream_handle(sd.device))
+    nat.native().sp_rows_dense(*csr_ptrs(sd), rows.data_ptr(), nat.ptr(dst), m, sd.shape[0],
+                               out.shape[0], sd.d, out.data_ptr(), out.stride(0),
+                               nat.stream_handle(sd.device))
     return out
 
 
 def sp_list_estep_torch(sd, C, rows=None, weights=None, xn=None, chunk_rows=TWIN_CHUNK):
     n = sd.shape[0]
-    rows = _row_list(sd, rows)
+    rows = row_list(sd, rows)
     m = n if rows is None else rows.numel()
     Cd = C.double()
     k = Cd.shape[0]
@@ -318,7 +277,7 @@ def sp_list_estep_torch(sd, C, rows=None, weights=None, xn=None, chunk_rows=TWIN
     labels = torch.empty(m, dtype=torch.int64, device=sd.device)
     mind = torch.empty(m, dtype=torch.float64, device=sd.device)
     col = torch.arange(k, dtype=torch.int64, device=sd.device)
-    for s, e in _chunks(m, chunk_rows):
+    for s, e in chunks(m, chunk_rows):
         if rows is None:
             Xc, xc = sd.dense_rows(s, e), xn[s:e]
         else:
@@ -338,17 +297,12 @@ def sp_list_estep(sd, C, rows=None, weights=None, xn=None, operand=None, inertia
     sum_t w_t mind[t]).  The lowest index wins exact ties."""
     if xn is None:
         xn = sp_row_norms(sd)
-    if not _native_ok(sd):
+    if not native_ok(sd):
         return sp_list_estep_torch(sd, C, rows, weights, xn)
     n = sd.shape[0]
-    rows = _row_list(sd, rows)
+    rows = row_list(sd, rows)
     m = n if rows is None else rows.numel()
-    k = C.shape[0]
-    check_k(k)
-    CT, cn = operand if operand is not None else center_operand(C)
-    assert CT.dtype == torch.float64 and CT.is_contiguous() and CT.shape[0] == sd.d
-    assert cn.dtype == torch.float64 and cn.numel() >= k
-    assert xn.dtype == torch.float64 and xn.numel() >= n
+    CT, cn, xn = _operand(sd, C, operand, xn)
     dev = sd.device
     w = None if weights is None else weights.to(torch.float64).contiguous()
     assert w is None or w.numel() == m
@@ -357,22 +311,21 @@ def sp_list_estep(sd, C, rows=None, weights=None, xn=None, operand=None, inertia
     part = torch.empty(_PARTS, dtype=torch.float64, device=dev)
     if inertia is None:
         inertia = torch.empty(1, dtype=torch.float64, device=dev)
-    nat.native().sp_list_estep(sd.indptr.data_ptr(), sd.indices.data_ptr(), sd.data.data_ptr(),
-                               CT.data_ptr(), cn.data_ptr(), xn.data_ptr(), nat.ptr(rows), 0, m, n,
-                               sd.d, int(k), CT.shape[1], nat.ptr(w), labels.data_ptr(),
-                               mind.data_ptr(), part.data_ptr(), inertia.data_ptr(),
-                               nat.stream_handle(dev))
+    nat.native().sp_list_estep(*csr_ptrs(sd), CT.data_ptr(), cn.data_ptr(), xn.data_ptr(),
+                               nat.ptr(rows), 0, m, n, sd.d, C.shape[0], CT.shape[1], nat.ptr(w),
+                               labels.data_ptr(), mind.data_ptr(), part.data_ptr(),
+                               inertia.data_ptr(), nat.stream_handle(dev))
     return labels, mind, inertia
 
 
 def sp_list_sums_torch(sd, rows, labels, k, weights=None, chunk_rows=TWIN_CHUNK):
     """(sums [k, d], wsum [k]) of the listed rows by ``index_add_`` in list order."""
-    rows = _row_list(sd, rows)
+    rows = row_list(sd, rows)
     m = sd.shape[0] if rows is None else rows.numel()
     sums = torch.zeros((k, sd.d), dtype=torch.float64, device=sd.device)
     wsum = torch.zeros(k, dtype=torch.float64, device=sd.device)
     lab = labels.to(torch.int64)
-    for s, e in _chunks(m, chunk_rows):
+    for s, e in chunks(m, chunk_rows):
         Xc = sd.dense_rows(s, e) if rows is None else sp_rows_dense_torch(sd, rows[s:e])
         if weights is None:
             wc = torch.ones(e - s, dtype=torch.float64, device=sd.device)
@@ -448,15 +401,14 @@ class MiniBatchState:
         if not self.native:
             self._sums = sp_list_sums_torch(sd, rows, labels, self.k, weights)
             return
-        rows = _row_list(sd, rows)
+        rows = row_list(sd, rows)
         m = sd.shape[0] if rows is None else rows.numel()
         self._exps = self.exps(m)
         w = None if weights is None else weights.to(torch.float64).contiguous()
         assert labels.dtype == torch.int32 and labels.is_contiguous() and labels.numel() == m
         assert (w is None or w.numel() == m) and sd.d == self.d
         k, d = self.k, self.d
-        nat.native().sp_list_mstep(sd.indptr.data_ptr(), sd.indices.data_ptr(),
-                                   sd.data.data_ptr(), nat.ptr(rows), 0, labels.data_ptr(),
+        nat.native().sp_list_mstep(*csr_ptrs(sd), nat.ptr(rows), 0, labels.data_ptr(),
                                    nat.ptr(w), m, sd.shape[0], d, k, self._exps[0], self._exps[1],
                                    self.q.data_ptr(), self.q[k * d:].data_ptr(),
                                    nat.stream_handle(self.device))

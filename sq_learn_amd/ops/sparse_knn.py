@@ -4,7 +4,7 @@ nearest fit rows of every query, ordered by (distance, fit index).
 
 Device path: ``csrc/spknn.hip`` - one workgroup per (query row, tile of
 ``tile`` fit rows).  The fit set is read through its cached transpose
-(``sparse_linalg.csr_transpose``) and a tile pointer table built once per
+(``_csr.csr_transpose``) and a tile pointer table built once per
 fit set (:func:`tile_table`), so a query nonzero in column c touches only the
 stored values of column c: the work is ``sum_c nnz_q(c) * nnz_x(c)``.  Inner
 products are accumulated as 64-bit integer quanta of ``2^e_i`` (one exponent
@@ -20,8 +20,8 @@ the same epilogue formulae and a stable sort on (distance, index).
 import torch
 
 from . import _native as nat
-from .sparse_kmeans import TWIN_CHUNK, _chunks, _native_ok, sp_row_norms, sp_row_norms_torch
-from .sparse_linalg import csr_transpose
+from ._csr import (TWIN_CHUNK, chunks, csr_ptrs, csr_transpose, native_ok, sp_row_norms,
+                   sp_row_norms_torch)
 from ..utils.pairwise import get_chunk_n_rows
 
 TILE_MAX = 8192        # 64 KiB of LDS accumulators: two workgroups per CU (csrc/spknn.hip)
@@ -134,6 +134,36 @@ def _select_block(D, kk):
     return D.gather(1, idx), idx
 
 
+# ---------------------------------------------------------------- operands
+class InvertedIndex:
+    """Operands of the inverted-index kernels (``csrc/spknn_acc.h``) for one
+    (fit set, queries, tile): the tile table, the cached transpose, the
+    squared row norms of both sides (``qn`` is ``xn`` in a self-join) and one
+    fixed-point exponent per query row."""
+
+    def __init__(self, fit_sd, query_sd, tile, xn=None, qn=None):
+        self.fit, self.qry, self.tile = fit_sd, query_sd, tile
+        self.n, self.d = fit_sd.shape
+        self.tab = tile_table(fit_sd, tile)
+        self.t = csr_transpose(fit_sd)
+        self.ntiles = -(-self.n // tile)
+        self.xn = sp_row_norms(fit_sd) if xn is None else xn
+        if qn is None:
+            qn = self.xn if query_sd is fit_sd else sp_row_norms(query_sd)
+        self.qn = qn
+        max_x = float(fit_sd.data.abs().max()) if fit_sd.nnz else 0.0
+        self.qexp = query_exps(query_sd, max_x)
+        self.lib = nat.native()
+
+    def args(self, a, b):
+        """The leading arguments of a launch on the query rows [a, b), the
+        same for ``sp_knn`` and ``sp_radius_mark``: nine pointers, then q0, m,
+        n, d, T, nnz_x."""
+        return (*csr_ptrs(self.qry), self.t.indices.data_ptr(), self.t.data.data_ptr(),
+                self.tab.data_ptr(), self.qn.data_ptr(), self.xn.data_ptr(),
+                self.qexp.data_ptr(), a, b - a, self.n, self.d, self.tile, self.t.nnz)
+
+
 # --------------------------------------------------------------------- op
 def _check(fit_sd, query_sd, kk):
     if fit_sd.shape[1] != query_sd.shape[1]:
@@ -156,22 +186,14 @@ def sp_knn(fit_sd, query_sd, kk, metric="euclidean", tile=None, rows=None, xn=No
     precomputed squared row norms of the two sides."""
     code = _metric_code(metric)
     kk = _check(fit_sd, query_sd, kk)
-    if not _native_ok(fit_sd):
+    if not native_ok(fit_sd):
         return sp_knn_torch(fit_sd, query_sd, kk, metric)
-    _native_ok(query_sd)
+    native_ok(query_sd)
     tile = _tile(tile)
-    n, d = fit_sd.shape
+    op = InvertedIndex(fit_sd, query_sd, tile, xn, qn)
+    n, ntiles = op.n, op.ntiles
     m = query_sd.shape[0]
     dev = fit_sd.device
-    tab = tile_table(fit_sd, tile)
-    t = csr_transpose(fit_sd)
-    ntiles = -(-n // tile)
-    if xn is None:
-        xn = sp_row_norms(fit_sd)
-    if qn is None:
-        qn = xn if query_sd is fit_sd else sp_row_norms(query_sd)
-    max_x = float(fit_sd.data.abs().max()) if fit_sd.nnz else 0.0
-    qexp = query_exps(query_sd, max_x)
     select = kk <= KMAX
     if rows is None:
         # partials: fp64 + int32 per (tile, slot); dist mode: the block, the
@@ -188,14 +210,11 @@ def sp_knn(fit_sd, query_sd, kk, metric="euclidean", tile=None, rows=None, xn=No
     else:
         pd = pi = None
         block = torch.empty((mc, n), dtype=torch.float64, device=dev)
-    fn = nat.native().sp_knn
     st = nat.stream_handle(dev)
-    for a, b in _chunks(m, rows):
-        fn(query_sd.indptr.data_ptr(), query_sd.indices.data_ptr(), query_sd.data.data_ptr(),
-           t.indices.data_ptr(), t.data.data_ptr(), tab.data_ptr(), qn.data_ptr(), xn.data_ptr(),
-           qexp.data_ptr(), a, b - a, n, d, tile, t.nnz, kk if select else 0, code,
-           0 if select else 1, nat.ptr(pd), nat.ptr(pi), nat.ptr(block),
-           D[a:b].data_ptr() if select else 0, idx[a:b].data_ptr() if select else 0, st)
+    for a, b in chunks(m, rows):
+        op.lib.sp_knn(*op.args(a, b), kk if select else 0, code, 0 if select else 1, nat.ptr(pd),
+                      nat.ptr(pi), nat.ptr(block), D[a:b].data_ptr() if select else 0,
+                      idx[a:b].data_ptr() if select else 0, st)
         if not select:
             D[a:b], idx[a:b] = _select_block(block[:b - a], kk)
     return D, idx
@@ -218,11 +237,11 @@ def sp_knn_torch(fit_sd, query_sd, kk, metric="euclidean", xn=None, qn=None,
         qn = xn if query_sd is fit_sd else sp_row_norms_torch(query_sd)
     D = torch.empty((m, kk), dtype=torch.float64, device=dev)
     idx = torch.empty((m, kk), dtype=torch.int64, device=dev)
-    for a, b in _chunks(m, chunk_rows):
+    for a, b in chunks(m, chunk_rows):
         Q = query_sd.dense_rows(a, b)
         bd = torch.empty((b - a, 0), dtype=torch.float64, device=dev)
         bi = torch.empty((b - a, 0), dtype=torch.int64, device=dev)
-        for s, e in _chunks(n, chunk_rows):
+        for s, e in chunks(n, chunk_rows):
             dot = Q @ fit_sd.dense_rows(s, e).T
             cd = torch.cat([bd, _distances(dot, qn[a:b].double(), xn[s:e].double(), code)], 1)
             ci = torch.cat([bi, torch.arange(s, e, dtype=torch.int64,

@@ -7,7 +7,7 @@ nonzeros, lanes across the columns of the dense operand, every nonzero one
 contiguous row gather; rows longer than a segment go through per-segment
 partials that a second kernel adds in segment order.  ``Y = X W`` runs the
 kernel on X, ``Z = X^T Y`` runs the same kernel on the CSR of X^T
-(:func:`csr_transpose`, built once per matrix with torch plumbing and cached
+(``_csr.csr_transpose``, built once per matrix with torch plumbing and cached
 on the ``SparseData``), so both products are gathers: no floating-point
 atomics, results bit-identical from run to run and independent of the launch
 geometry.  A GPU input always takes the native path and raises when the
@@ -18,30 +18,9 @@ chunks, as ``ops/sparse_kmeans.py`` does.
 import torch
 
 from . import _native as nat
-from .sparse_kmeans import TWIN_CHUNK, _chunks, _native_ok
+from ._csr import TWIN_CHUNK, chunks, csr_ptrs, csr_transpose, native_ok
 
 SEG_DEFAULT = 1024     # nonzeros per unit of work (one wave)
-
-
-# --------------------------------------------------------------- transpose
-def csr_transpose(sd):
-    """X^T as canonical CSR on the device of ``sd`` (cached on ``sd``): a
-    stable sort of the column indices keeps the row order inside every
-    column, so the transposed rows come out sorted."""
-    if sd._transpose is not None:
-        return sd._transpose
-    from ..models._data import SparseData
-    n, d = sd.shape
-    if n >= 2 ** 31:
-        raise ValueError("csr_transpose supports fewer than 2^31 rows (int32 indices)")
-    cols = sd.indices.to(torch.int64)
-    order = torch.sort(cols, stable=True).indices
-    rows = sd.row_ids()[order].to(torch.int32)
-    indptr = torch.zeros(d + 1, dtype=torch.int64, device=sd.device)
-    if sd.nnz:
-        indptr[1:] = torch.cumsum(torch.bincount(cols, minlength=d), 0)
-    sd._transpose = SparseData(indptr, rows, sd.data[order].contiguous(), (d, n))
-    return sd._transpose
 
 
 # ----------------------------------------------------------- segment table
@@ -132,18 +111,17 @@ def sp_xw(sd, W, out=None, seg=None):
             or (out.shape[1] > 1 and out.stride(1) != 1) or out.device != dev:
         raise ValueError("out must be an fp64 matrix of at least n x l with unit column stride "
                          "on the device of the sparse matrix")
-    if not _native_ok(sd):
+    if not native_ok(sd):
         return sp_xw_torch(sd, Wd, out)
     if Wd.stride(1) != 1 or Wd.stride(0) < l:
         Wd = Wd.contiguous()
     tab = segments(sd, seg)
     scratch = torch.empty(max(tab.slots * l, 1), dtype=torch.float64, device=dev)
     ldo = out.stride(0) if n > 1 else max(out.stride(0), l)
-    nat.native().spmm(sd.indptr.data_ptr(), sd.indices.data_ptr(), sd.data.data_ptr(),
-                      tab.row.data_ptr(), tab.start.data_ptr(), tab.dst.data_ptr(), tab.nseg,
-                      tab.seg, tab.long_row.data_ptr(), tab.long_ptr.data_ptr(), tab.nlong,
-                      Wd.data_ptr(), max(Wd.stride(0), l), l, out.data_ptr(), ldo,
-                      scratch.data_ptr(), nat.stream_handle(dev))
+    nat.native().spmm(*csr_ptrs(sd), tab.row.data_ptr(), tab.start.data_ptr(),
+                      tab.dst.data_ptr(), tab.nseg, tab.seg, tab.long_row.data_ptr(),
+                      tab.long_ptr.data_ptr(), tab.nlong, Wd.data_ptr(), max(Wd.stride(0), l), l,
+                      out.data_ptr(), ldo, scratch.data_ptr(), nat.stream_handle(dev))
     return out[:n, :l]
 
 
@@ -153,7 +131,7 @@ def sp_xw_torch(sd, W, out=None):
     Wd = W.to(torch.float64)
     if out is None:
         out = torch.empty((n, l), dtype=torch.float64, device=sd.device)
-    for a, b in _chunks(n, TWIN_CHUNK):
+    for a, b in chunks(n, TWIN_CHUNK):
         out[a:b, :l] = sd.dense_rows(a, b) @ Wd
     return out[:n, :l]
 
@@ -164,7 +142,7 @@ def sp_xty(sd, Y, seg=None):
     if Y.dim() != 2 or Y.shape[0] != n:
         raise ValueError(f"operand of shape {tuple(Y.shape)} does not match a matrix with {n} "
                          "rows")
-    if not _native_ok(sd):
+    if not native_ok(sd):
         return sp_xty_torch(sd, Y.to(sd.device))
     return sp_xw(csr_transpose(sd), Y, seg=seg)
 
@@ -173,17 +151,17 @@ def sp_xty_torch(sd, Y):
     n, d = sd.shape
     Yd = Y.to(torch.float64)
     Z = torch.zeros((d, Y.shape[1]), dtype=torch.float64, device=sd.device)
-    for a, b in _chunks(n, TWIN_CHUNK):
+    for a, b in chunks(n, TWIN_CHUNK):
         Z += sd.dense_rows(a, b).T @ Yd[a:b]
     return Z
 
 
 def sp_power_iter(sd, Z):
     """X^T (X Z) in fp64 [d, l]: one step of the range finder."""
-    if not _native_ok(sd):
+    if not native_ok(sd):
         Zd = Z.to(device=sd.device, dtype=torch.float64)
         out = torch.zeros_like(Zd)
-        for a, b in _chunks(sd.shape[0], TWIN_CHUNK):
+        for a, b in chunks(sd.shape[0], TWIN_CHUNK):
             Xc = sd.dense_rows(a, b)
             out += Xc.T @ (Xc @ Zd)
         return out
@@ -194,7 +172,7 @@ def sp_col_moments(sd):
     """(sum, sum of squares) of every column over the rows, fp64 [d] each:
     the row moments of the cached transpose (fixed summation order)."""
     d = sd.shape[1]
-    if not _native_ok(sd):
+    if not native_ok(sd):
         return sp_col_moments_torch(sd)
     t = csr_transpose(sd)
     s = torch.empty(d, dtype=torch.float64, device=sd.device)

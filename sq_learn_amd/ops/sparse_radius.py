@@ -20,9 +20,8 @@ import numpy as np
 import torch
 
 from . import _native as nat
-from .sparse_kmeans import TWIN_CHUNK, _chunks, _native_ok, sp_row_norms, sp_row_norms_torch
-from .sparse_knn import TILE_MAX, _MAX_GRID, _distances, _metric_code, query_exps, tile_table
-from .sparse_linalg import csr_transpose
+from ._csr import TWIN_CHUNK, chunks, native_ok, sp_row_norms_torch
+from .sparse_knn import TILE_MAX, _MAX_GRID, InvertedIndex, _distances, _metric_code
 from ..utils.pairwise import get_chunk_n_rows
 
 TILE_DEFAULT = 4096    # fit rows per workgroup; the fastest measured (profiles/sparse_dbscan.md)
@@ -58,23 +57,12 @@ def _result(ends, parts, m):
     return indptr, indices.astype(np.int64, copy=False)
 
 
-class _Plan:
-    """Operands of the two kernels for one (fit set, queries, tile)."""
+class _Plan(InvertedIndex):
+    """The inverted-index operands plus the mask geometry of the two kernels."""
 
     def __init__(self, fit_sd, query_sd, tile, xn=None, qn=None):
-        self.fit, self.qry, self.tile = fit_sd, query_sd, tile
-        self.n, self.d = fit_sd.shape
-        self.tab = tile_table(fit_sd, tile)
-        self.t = csr_transpose(fit_sd)
-        self.ntiles = -(-self.n // tile)
+        super().__init__(fit_sd, query_sd, tile, xn, qn)
         self.words = -(-self.n // 64)
-        self.xn = sp_row_norms(fit_sd) if xn is None else xn
-        if qn is None:
-            qn = self.xn if query_sd is fit_sd else sp_row_norms(query_sd)
-        self.qn = qn
-        max_x = float(fit_sd.data.abs().max()) if fit_sd.nnz else 0.0
-        self.qexp = query_exps(query_sd, max_x)
-        self.lib = nat.native()
 
     def buffers(self, rows):
         dev = self.fit.device
@@ -84,12 +72,8 @@ class _Plan:
     def mark(self, a, b, thr, code, include_self, mask, cnt):
         """Query rows [a, b): one bit per pair into ``mask``, hits per
         (query, tile) into ``cnt``."""
-        q, t = self.qry, self.t
-        self.lib.sp_radius_mark(q.indptr.data_ptr(), q.indices.data_ptr(), q.data.data_ptr(),
-                                t.indices.data_ptr(), t.data.data_ptr(), self.tab.data_ptr(),
-                                self.qn.data_ptr(), self.xn.data_ptr(), self.qexp.data_ptr(), a,
-                                b - a, self.n, self.d, self.tile, t.nnz, code, thr,
-                                1 if include_self else 0, mask.data_ptr(), cnt.data_ptr(),
+        self.lib.sp_radius_mark(*self.args(a, b), code, thr, 1 if include_self else 0,
+                                mask.data_ptr(), cnt.data_ptr(),
                                 nat.stream_handle(self.fit.device))
 
     def fill(self, rows, mask, cs, total):
@@ -115,9 +99,9 @@ def sp_radius(fit_sd, query_sd, thr, metric="euclidean", include_self=False, til
     code = _metric_code(metric)
     thr = _check(fit_sd, query_sd, thr, include_self)
     tile = _tile(tile)
-    if not _native_ok(fit_sd):
+    if not native_ok(fit_sd):
         return sp_radius_torch(fit_sd, query_sd, thr, metric, include_self, xn=xn, qn=qn)
-    _native_ok(query_sd)
+    native_ok(query_sd)
     plan = _Plan(fit_sd, query_sd, tile, xn, qn)
     m = query_sd.shape[0]
     ntiles = plan.ntiles
@@ -129,7 +113,7 @@ def sp_radius(fit_sd, query_sd, thr, metric="euclidean", include_self=False, til
     mask, cnt = plan.buffers(min(rows, m))
     ends, parts = [], []
     total = 0
-    for a, b in _chunks(m, rows):
+    for a, b in chunks(m, rows):
         plan.mark(a, b, thr, code, include_self, mask, cnt)
         cs = torch.cumsum(cnt[:b - a].reshape(-1), 0, dtype=torch.int64)
         row_end = cs[ntiles - 1::ntiles].cpu().numpy()     # the host read of the chunk
@@ -157,10 +141,10 @@ def sp_radius_torch(fit_sd, query_sd, thr, metric="euclidean", include_self=Fals
     q_rows = max(1, min(int(chunk_rows), get_chunk_n_rows(max(n, 1))))
     ends, parts = [], []
     total = 0
-    for a, b in _chunks(m, q_rows):
+    for a, b in chunks(m, q_rows):
         Q = query_sd.dense_rows(a, b)
         hit = torch.empty((b - a, n), dtype=torch.bool, device=fit_sd.device)
-        for s, e in _chunks(n, chunk_rows):
+        for s, e in chunks(n, chunk_rows):
             dot = Q @ fit_sd.dense_rows(s, e).T
             hit[:, s:e] = _distances(dot, qn[a:b], xn[s:e], code) <= thr
         if include_self:

@@ -257,6 +257,28 @@ def test_scatter_random_within_quantisation(cases, k):
     assert torch.equal(st.CT.cpu(), S.center_operand(Ct)[0])
 
 
+def test_zero_weight_quantum_rule(cuda):
+    """The one difference between the two scatters.  Row 3's weight is below
+    half a weight quantum (rn(0.4) = 0) while its weighted value is above half
+    a value quantum (rn(0.4 * 3.5 / 2) = rn(0.7) = 1): the Lloyd M-step keeps
+    that value quantum, the mini-batch scatter drops the whole position."""
+    v, w = 3.5, [1.03, 1.0, 1.0, 0.4 * 2.0 ** -49]
+    assert K.fixed_point_exp(v * 1.03, 4) == -48 and K.fixed_point_exp(1.03, 4) == -49
+    qx = [round(wi * v * 2.0 ** 48) for wi in w]
+    qw = [round(wi * 2.0 ** 49) for wi in w]
+    assert qx[3] == 1 and qw[3] == 0
+    sd = as_sparse_data(sp.csr_matrix(np.full((4, 1), v)), device=cuda)
+    wt = torch.as_tensor(w, dtype=torch.float64, device=cuda)
+    labels = torch.zeros(4, dtype=torch.int32, device=cuda)
+    sums, counts = S.sp_centroid_sums(sd, labels, 1, wt)
+    assert float(sums[0, 0]) == float(sum(qx[:3]) + 1) * 2.0 ** -48
+    assert float(counts[0]) == float(sum(qw[:3])) * 2.0 ** -49
+    st = S.MiniBatchState(cuda, torch.zeros((1, 1)), torch.zeros(1), max_abs=v, max_w=1.03)
+    st.scatter(sd, None, labels, wt)
+    assert st.exps(4) == (-48, -49)
+    assert st.q.tolist() == [sum(qx[:3]), sum(qw[:3])]
+
+
 # ---------------------------------------------------------------- kernel d
 @pytest.mark.parametrize("kind", ["exact", "random"])
 def test_rows_dense(cases, kind):
