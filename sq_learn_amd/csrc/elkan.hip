@@ -20,6 +20,7 @@
 // upper bound is below half the distance to their nearest other centre skip
 // all distance work (Elkan's lemma 1).
 #include "common.h"
+#include "sq_api.h"
 
 namespace sq {
 

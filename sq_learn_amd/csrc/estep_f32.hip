@@ -43,6 +43,7 @@
 #include "common.h"
 #include "band.h"
 #include "f16_tile.h"
+#include "sq_api.h"
 
 namespace sq {
 
@@ -1217,8 +1218,8 @@ __global__ void __launch_bounds__(256) bounds_filter_kernel(
   }
 }
 
-// the gap records of the calling thread's next filter / screen launches (null
-// rec: off) - set by the engine before each certified E-step
+// the gap records of one certified E-step's filter / screen launches (null
+// rec: off) - built by sq_estep_x64 from its trailing arguments
 struct MultiRec {
   GapRec* rec = nullptr;
   int* mflag = nullptr;            // the per-row multi flag (2 + record base)
@@ -1233,50 +1234,23 @@ struct MultiRec {
   long long* mrows_mv = nullptr;   // list-B rows whose label can have moved (the gap
   int* count_mv = nullptr;         // screen: new argmin, or forwarded to the multi list)
 };
-static thread_local MultiRec g_mrec;
-// second overflow list of the dense-row 3-pass kernel (null: off) - the
-// calling thread's next certified E-steps
+// second overflow list of the dense-row 3-pass kernel (null: off)
 struct Ovf2 {
   void* rows = nullptr;   // int64 [cap]
   int* count = nullptr;   // int32 [1], zeroed with the E-step's counters
 };
-static thread_local Ovf2 g_ovf2;
-extern "C" int sq_set_overflow2(void* rows, void* count) {
-  g_ovf2.rows = rows;
-  g_ovf2.count = (int*)count;
-  return (rows != nullptr) != (count != nullptr) ? (int)hipErrorInvalidValue : 0;
-}
-extern "C" int sq_multi_records(void* rec, void* mflag, int it_now, int it_lo, int ring,
-                                const void* dsh, const void* dq, long long dsh_stride,
-                                void* mrows_b, void* count_b, void* n_done, void* mrows_mv,
-                                void* count_mv) {
-  g_mrec.rec = (GapRec*)rec;
-  g_mrec.mflag = (int*)mflag;
-  g_mrec.it_now = it_now;
-  g_mrec.it_lo = it_lo;
-  g_mrec.ring = ring;
-  g_mrec.dsh = (const _Float16*)dsh;
-  g_mrec.dq = (const float*)dq;
-  g_mrec.dsh_stride = dsh_stride;
-  g_mrec.mrows_b = (long long*)mrows_b;
-  g_mrec.count_b = (int*)count_b;
-  g_mrec.n_done = (int*)n_done;
-  g_mrec.mrows_mv = (long long*)mrows_mv;
-  g_mrec.count_mv = (int*)count_mv;
-  if ((mrows_mv != nullptr) != (count_mv != nullptr)) return (int)hipErrorInvalidValue;
-  return (rec && (it_now < 1 || it_lo < 1 || it_lo > it_now || ring < 2 || ring > 16 || !mflag ||
-                  !dsh || !dq || !mrows_b || !count_b))
-             ? (int)hipErrorInvalidValue
-             : 0;
-}
 
 // rcount and multi_count must be zero on entry (the caller clears them with
-// the E-step's other counters in one fill).
+// the E-step's other counters in one fill).  rec_on: the gap records are on -
+// rows with a record of base in [it_lo, it_now - 1] go to mrows_b / count_b.
 extern "C" int sq_bounds_filter(const void* labels, void* ub, void* lb, const void* shift,
                                 const void* smax, long long n, double delta, void* rlist,
                                 void* rcount, const void* mflag, void* mrows, void* multi_count,
                                 const void* cc, const void* fidx, int nf, int k, void* stream,
-                                void* corr, void* rec_count) {
+                                void* corr, void* rec_count, int rec_on, int it_now, int it_lo,
+                                void* mrows_b, void* count_b) {
+  if (rec_on && (it_now < 1 || it_lo < 1 || it_lo > it_now || !mrows_b || !count_b))
+    return (int)hipErrorInvalidValue;
   if (n <= 0) return 0;
   if (!mflag || !mrows || !multi_count) return (int)hipErrorInvalidValue;
   if (nf < 0 || nf > 64 || (nf > 0 && (!cc || !fidx || k <= nf))) return (int)hipErrorInvalidValue;
@@ -1313,8 +1287,8 @@ extern "C" int sq_bounds_filter(const void* labels, void* ub, void* lb, const vo
                      (const double*)shift, (const double*)smax, n, delta, (long long*)rlist,
                      (int*)rcount, (const int*)mflag, (long long*)mrows, (int*)multi_count,
                      (const float*)cc, (const int*)fidx, nf, k,
-                     g_mrec.rec ? 1 : 0, g_mrec.it_now, g_mrec.it_lo, g_mrec.mrows_b,
-                     g_mrec.count_b, (float*)corr, (int*)rec_count);
+                     rec_on ? 1 : 0, it_now, it_lo, (long long*)mrows_b, (int*)count_b,
+                     (float*)corr, (int*)rec_count);
   return (int)hipGetLastError();
 }
 
@@ -2298,13 +2272,6 @@ __global__ void __launch_bounds__(256) centers_f16_operand_kernel(const float* _
 
 using namespace sq;
 
-extern "C" int sq_sum_partials(const void* part, int n, void* out, void* stream);
-extern "C" int sq_rows_f64(const void* X, long long ldx, const void* C, long long ldc, int d, int k,
-                           const void* rows, const void* count, long long n_direct, long long cap,
-                           void* labels, void* mind, void* corr, void* ub, double delta,
-                           unsigned k0, unsigned k1, unsigned s0, unsigned s1,
-                           long long row_offset, int grid, void* stream);
-
 template <int KSD, int TOP = 2>
 static int launch_estep_f32(const void* X, const void* C, const void* xn, void* labels, void* mind,
                             void* ovf_rows, void* ovf_count, void* part, int part_cap,
@@ -2349,7 +2316,7 @@ static int launch_estep_x64(const void* Xh, const void* X, const void* C, const 
                             float delta_s, double delta, RngKey key, long long row_offset,
                             int dense_cap, hipStream_t st, const void* rlist, const void* rcount,
                             void* ub, void* lb, void* mflag, void* xflag, int list_rs,
-                            bool defer_rows = false) {
+                            const MultiRec& mrec, bool defer_rows = false) {
   // list mode (the rows the bounds could not prune): one row set per wave -
   // half the rows per workgroup, so a short list (the per-GPU share of a
   // strong-scaled run) finishes in one half-length sweep; a full sweep keeps
@@ -2397,7 +2364,7 @@ static int launch_estep_x64(const void* Xh, const void* X, const void* C, const 
   // with xrows the fp32 screen first, the fp64 pass over what it left
   const long long rblocks = (n / 16 + 63) / 64;
   const unsigned rgrid = (unsigned)(rblocks < 4096 ? (rblocks > 0 ? rblocks : 1) : 4096);
-  if (xflag && g_mrec.rec && ub) {
+  if (xflag && mrec.rec && ub) {
     if constexpr (KSD * 16 % 128 == 0) {
       // list B first: its uncertain rows join the multi list
       // one resident round of long-lived waves (each takes blocks of 64 rows)
@@ -2412,12 +2379,12 @@ static int launch_estep_x64(const void* Xh, const void* X, const void* C, const 
       }
       const unsigned bgrid = (unsigned)min(max(rblocks, 1LL), gres);
       hipLaunchKernelGGL(gap_screen_kernel<KSD * 16>, dim3(bgrid), dim3(256), 0, st,
-                         (const _Float16*)Xh, (const float*)xn, g_mrec.mrows_b, g_mrec.count_b,
-                         g_mrec.dsh, g_mrec.dsh_stride, g_mrec.dq,
-                         g_mrec.dsh_stride / (KSD * 16) * 8, 1.0f / alpha, (float)delta,
-                         (int*)labels, g_mrec.rec, g_mrec.mflag, g_mrec.it_now, g_mrec.ring,
-                         max(1, g_mrec.ring / 2), (long long*)mrows, (int*)multi_count, n,
-                         g_mrec.n_done, g_mrec.mrows_mv, g_mrec.count_mv);
+                         (const _Float16*)Xh, (const float*)xn, mrec.mrows_b, mrec.count_b,
+                         mrec.dsh, mrec.dsh_stride, mrec.dq,
+                         mrec.dsh_stride / (KSD * 16) * 8, 1.0f / alpha, (float)delta,
+                         (int*)labels, mrec.rec, mrec.mflag, mrec.it_now, mrec.ring,
+                         max(1, mrec.ring / 2), (long long*)mrows, (int*)multi_count, n,
+                         mrec.n_done, mrec.mrows_mv, mrec.count_mv);
     }
   }
   if (xflag) {
@@ -2437,7 +2404,7 @@ static int launch_estep_x64(const void* Xh, const void* X, const void* C, const 
     hipLaunchKernelGGL(fk, dim3(fgrid2), dim3(256), 0, st, (const float*)X, (const float*)Cm,
                        (const long long*)mrows, (const int*)mcand, (const int*)multi_count,
                        (int*)labels, (float*)mind, n, delta, (float*)ub, (unsigned char*)xflag,
-                       sil, g_mrec.rec, g_mrec.mflag, g_mrec.it_now, key, row_offset,
+                       sil, mrec.rec, mrec.mflag, mrec.it_now, key, row_offset,
                        (float*)corr);
   }
   // (defer_rows: the caller launches it after the dense-row passes, which
@@ -2496,13 +2463,27 @@ int sq_estep_f32(const void* X, const void* C, const void* xn, void* labels, voi
 // whose distance the M-step (or fill_mind) computes; no inertia here.
 // Xh: fp16(alpha x) [n][d_pad]; X: fp32 [n][d_pad]; Cm: fp32 centroids
 // [k][d_pad] (zero-padded like X); C: the fp16-split operand.
+// rec .. count_mv: the gap records (MultiRec; rec null: off); ovf2_rows /
+// ovf2_count: the second overflow list (Ovf2; null: off).
 int sq_estep_x64(const void* Xh, const void* X, const void* C, const void* Cm, const void* xn,
                  const void* cmax2, void* labels, void* mind, void* dense_rows, void* ovf_rows,
                  void* mrows, void* mcand, void* corr, void* rlist, void* rcount, void* ub,
-                 void* lb, void* mflag, void* xflag, void* counts, void* part, int part_cap, long long n, int d, int d_pad,
-                 int k,
-                 int k_pad, double alpha, double delta, unsigned k0, unsigned k1, unsigned s0,
-                 unsigned s1, long long row_offset, int list_rs, void* stream) {
+                 void* lb, void* mflag, void* xflag, void* counts, void* part, int part_cap,
+                 long long n, int d, int d_pad, int k, int k_pad, double alpha, double delta,
+                 unsigned k0, unsigned k1, unsigned s0, unsigned s1, long long row_offset,
+                 int list_rs, void* stream, void* rec, void* rec_mflag, int it_now, int it_lo,
+                 int ring, const void* dsh, const void* dq, long long dsh_stride, void* mrows_b,
+                 void* count_b, void* n_done, void* mrows_mv, void* count_mv, void* ovf2_rows,
+                 void* ovf2_count) {
+  if ((ovf2_rows != nullptr) != (ovf2_count != nullptr)) return (int)hipErrorInvalidValue;
+  if ((mrows_mv != nullptr) != (count_mv != nullptr)) return (int)hipErrorInvalidValue;
+  if (rec && (it_now < 1 || it_lo < 1 || it_lo > it_now || ring < 2 || ring > 16 || !rec_mflag ||
+              !dsh || !dq || !mrows_b || !count_b))
+    return (int)hipErrorInvalidValue;
+  const MultiRec mrec{(GapRec*)rec, (int*)rec_mflag, it_now, it_lo, ring, (const _Float16*)dsh,
+                      (const float*)dq, dsh_stride, (long long*)mrows_b, (int*)count_b,
+                      (int*)n_done, (long long*)mrows_mv, (int*)count_mv};
+  const Ovf2 ovf2{ovf2_rows, (int*)ovf2_count};
   if (n <= 0) return 0;
   if (k_pad % kTileN != 0 || k_pad <= 0 || k_pad > 32768 || k > k_pad || d > d_pad)
     return (int)hipErrorInvalidValue;
@@ -2530,16 +2511,16 @@ int sq_estep_x64(const void* Xh, const void* X, const void* C, const void* Cm, c
     rc = launch_estep_x64<KSD>(Xh, X, C, Cm, xn, cmax2, labels, mind, dense_rows, cnt + 1,       \
                                mrows, mcand, cnt + 2, corr, n, k_pad, fa, ds, delta, key,        \
                                row_offset, cap, st, rlist, rcount, ub, lb, mflag, xflag,         \
-                               list_rs, true);                                                   \
+                               list_rs, mrec, true);                                             \
     if (rc) return rc;                                                                           \
     rc = launch_estep_f32<KSD>(X, C, xn, labels, mind, ovf_rows, cnt, part, part_cap, nullptr,   \
                                n, k_pad, fa, ia2, ds, key, row_offset, cap, st, dense_rows,       \
                                cnt + 1, cmax2, mrows, mcand, cnt + 2, xflag, n);                 \
     if (rc) return rc;                                                                           \
-    if (g_ovf2.rows) {                                                                           \
+    if (ovf2.rows) {                                                                             \
       /* the overflow rows once more with 3 members per lane; what still */                      \
       /* overflows goes to the fp64 rows kernel */                                               \
-      rc = launch_estep_f32<KSD, 3>(X, C, xn, labels, mind, g_ovf2.rows, g_ovf2.count, part,     \
+      rc = launch_estep_f32<KSD, 3>(X, C, xn, labels, mind, ovf2.rows, ovf2.count, part,         \
                                     part_cap, nullptr, n, k_pad, fa, ia2, ds, key, row_offset,   \
                                     cap, st, ovf_rows, cnt, cmax2, mrows, mcand, cnt + 2, xflag, \
                                     n);                                                          \
@@ -2555,8 +2536,8 @@ int sq_estep_x64(const void* Xh, const void* X, const void* C, const void* Cm, c
                        (const int*)mcand, (const int*)(cnt + 2), (int*)labels, (float*)mind, n,  \
                        delta, key, row_offset, (float*)corr, (float*)ub,                         \
                        (const unsigned char*)xflag);                                             \
-    rc = sq_rows_f64(X, d_pad, Cm, d_pad, d_pad, k, g_ovf2.rows ? g_ovf2.rows : ovf_rows,        \
-                     g_ovf2.rows ? g_ovf2.count : cnt, 0, n, labels, mind, corr,                  \
+    rc = sq_rows_f64(X, d_pad, Cm, d_pad, d_pad, k, ovf2.rows ? ovf2.rows : ovf_rows,            \
+                     ovf2.rows ? ovf2.count : cnt, 0, n, labels, mind, corr,                     \
                      ub, delta, k0, k1, s0, s1, row_offset, (int)fgrid, stream);                 \
     break;
     CASE(1) CASE(2) CASE(4) CASE(8) CASE(16)
@@ -2567,7 +2548,7 @@ int sq_estep_x64(const void* Xh, const void* X, const void* C, const void* Cm, c
     rc = launch_estep_x64<KSD>(Xh, X, C, Cm, xn, cmax2, labels, mind, dense_rows, cnt + 1,       \
                                mrows, mcand, cnt + 2, corr, n, k_pad, fa, ds, delta, key,        \
                                row_offset, cap, st, rlist, rcount, ub, lb, mflag, xflag,         \
-                               list_rs);                                                         \
+                               list_rs, mrec);                                                   \
     if (rc) return rc;                                                                           \
     rc = sq_rows_f64(X, d_pad, Cm, d_pad, d_pad, k, dense_rows, cnt + 1, 0, n, labels, mind,      \
                      corr, ub, delta, k0, k1, s0, s1, row_offset, (int)fgrid, stream);           \

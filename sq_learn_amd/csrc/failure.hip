@@ -9,6 +9,7 @@
 // failure_inject_torch).  counters[0] += attempts made, counters[1] +=
 // corrupted rows (wave-reduced, one 64-bit atomic per wave per counter).
 #include "common.h"
+#include "sq_api.h"
 
 namespace sq {
 

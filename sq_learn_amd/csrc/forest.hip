@@ -14,6 +14,7 @@
 //   leaf-id intermediate in HBM; optional NaN routing (missing_left) for the
 //   histogram-GBDT predictors.
 #include "common.h"
+#include "sq_api.h"
 
 namespace sq {
 

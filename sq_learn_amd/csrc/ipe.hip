@@ -32,6 +32,7 @@
 // 16 lanes of a row merge their (D~, tie key, j) minima, then the 4 waves.
 
 #include "ipe_law.h"
+#include "sq_api.h"
 
 namespace sq {
 

@@ -46,6 +46,7 @@
 // then an xor tree over the 16 lanes (ipe_hint_kernel's order).
 #include "ipe_law.h"
 #include "f16_tile.h"
+#include "sq_api.h"
 #include <cmath>
 
 namespace sq {

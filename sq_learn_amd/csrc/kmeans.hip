@@ -28,6 +28,7 @@
 #include "fejer.h"
 #include "band.h"
 #include "f16_tile.h"
+#include "sq_api.h"
 
 namespace sq {
 

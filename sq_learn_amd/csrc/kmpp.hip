@@ -35,6 +35,7 @@
 // next screen / pick reads the improving rows' D from the mask), so no pass
 // touches rows that did not change.
 #include "common.h"
+#include "sq_api.h"
 
 namespace sq {
 

@@ -10,6 +10,7 @@
 // with fewer than kk candidates (kk > nref, or NaN entries) is padded with
 // (+inf, -1); col_offset is added to real columns only.
 #include "common.h"
+#include "sq_api.h"
 
 namespace sq {
 

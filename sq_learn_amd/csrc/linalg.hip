@@ -6,6 +6,7 @@
 //              (Utility.py:196-231).
 // row_norms  : ||x_i||^2 for bf16/fp32 rows.
 #include "common.h"
+#include "sq_api.h"
 #include <type_traits>
 
 namespace sq {

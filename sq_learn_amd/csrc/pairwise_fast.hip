@@ -13,6 +13,7 @@
 // with one padding column, so the per-thread column reads are conflict-free),
 // and each thread accumulates a 4 x 4 sub-block in registers.
 #include "common.h"
+#include "sq_api.h"
 
 namespace sq {
 

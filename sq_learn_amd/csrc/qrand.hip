@@ -4,6 +4,7 @@
 // a row-sharded job draws identical numbers for the same global element.
 #include "common.h"
 #include "fejer.h"
+#include "sq_api.h"
 
 namespace sq {
 

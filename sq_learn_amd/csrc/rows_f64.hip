@@ -28,6 +28,7 @@
 // incremental M-step's correction) and ub = |x - c_label| (Hamerly).
 #include "common.h"
 #include "band.h"
+#include "sq_api.h"
 
 namespace sq {
 

@@ -24,6 +24,7 @@
 //   Row norms: sp_row_moments_kernel of sp_rows.h without the sum.
 #include "band.h"
 #include "sp_rows.h"
+#include "sq_api.h"
 
 namespace sq {
 

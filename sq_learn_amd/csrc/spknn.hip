@@ -38,6 +38,7 @@
 // The accumulate phase and the distance formulae live in spknn_acc.h, shared
 // with the radius-neighbour kernels of spradius.hip.
 #include "spknn_acc.h"
+#include "sq_api.h"
 
 namespace sq {
 

@@ -21,6 +21,7 @@
 //     mb_record_kernel sum in a fixed order.
 //   sp_rows_dense_kernel: one wave per list entry, zero fill then scatter.
 #include "sp_rows.h"
+#include "sq_api.h"
 
 namespace sq {
 

@@ -29,6 +29,7 @@
 //     these are the column moments.
 // The segment walk is sp_walk of sp_rows.h with the clamped column offsets.
 #include "sp_rows.h"
+#include "sq_api.h"
 
 namespace sq {
 

@@ -30,6 +30,7 @@
 //
 // No floating-point atomics, no per-lane lists.  LDS: 8 T + 16 bytes.
 #include "spknn_acc.h"
+#include "sq_api.h"
 
 namespace sq {
 

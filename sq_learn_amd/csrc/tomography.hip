@@ -18,6 +18,7 @@
 // The host picks first[row] = the first checkpoint with err <= delta (the
 // reference's stopping rule) between the two launches.
 #include "common.h"
+#include "sq_api.h"
 
 namespace sq {
 

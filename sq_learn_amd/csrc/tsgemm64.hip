@@ -26,6 +26,7 @@
 // B[k = l >> 4][j = l & 15]; C/D: lane l, register r -> (row (l >> 4) + 4 r,
 // col l & 15).
 #include "common.h"
+#include "sq_api.h"
 #include <type_traits>
 
 namespace sq {

@@ -8,6 +8,7 @@ Philox keys (reference ``_dmeans.py:732-830``).
 
 import math
 import os
+from typing import NamedTuple
 
 import numpy as np
 
@@ -306,22 +307,20 @@ def ipe_fused_native(X, Cfrag, xn, cn, k, k_pad, d_pad, eps, Q, key: RngKey, tie
         assert ext[0].dtype == torch.float32 and ext[1].dtype == torch.int32
     elif hint_labels is not None and prune and int(Q) % 2 == 1 and layout != 3:
         scratch = torch.empty(2 * max(n, 1), dtype=torch.int32, device=X.device)
-    rc = nat.native().ipe_fused(X.data_ptr(), X.stride(0), Cfrag.data_ptr(),
-                                0 if C is None else C.data_ptr(),
-                                0 if hint_labels is None else hint_labels.data_ptr(),
-                                xn.data_ptr(), cn.data_ptr(), labels.data_ptr(), mind.data_ptr(), n,
-                                d, d_pad, k, k_pad, float(eps), int(Q), key.k0, key.k1, key.s0,
-                                key.s1, tie_key.k0, tie_key.k1, tie_key.s0, tie_key.s1,
-                                skip_key.k0, skip_key.k1, skip_key.s0, skip_key.s1,
-                                int(row_offset), int(bool(prune)) | (int(layout) & 3) << 1,
-                                0 if stats is None else stats.data_ptr(),
-                                0 if scratch is None else scratch.data_ptr(),
-                                nat.stream_handle(X.device),
-                                *((rows[0].data_ptr(), rows[1].data_ptr(), int(rows[2]),
-                                   ext[0].data_ptr(), ext[1].data_ptr()) if rows is not None
-                                  else ()))
-    if rc:
-        raise RuntimeError(f"ipe_fused failed (hip error {rc})")
+    nat.native().ipe_fused(X.data_ptr(), X.stride(0), Cfrag.data_ptr(),
+                           0 if C is None else C.data_ptr(),
+                           0 if hint_labels is None else hint_labels.data_ptr(),
+                           xn.data_ptr(), cn.data_ptr(), labels.data_ptr(), mind.data_ptr(), n,
+                           d, d_pad, k, k_pad, float(eps), int(Q), key.k0, key.k1, key.s0,
+                           key.s1, tie_key.k0, tie_key.k1, tie_key.s0, tie_key.s1,
+                           skip_key.k0, skip_key.k1, skip_key.s0, skip_key.s1,
+                           int(row_offset), int(bool(prune)) | (int(layout) & 3) << 1,
+                           0 if stats is None else stats.data_ptr(),
+                           0 if scratch is None else scratch.data_ptr(),
+                           nat.stream_handle(X.device),
+                           *((rows[0].data_ptr(), rows[1].data_ptr(), int(rows[2]),
+                              ext[0].data_ptr(), ext[1].data_ptr()) if rows is not None
+                             else (0, 0, 0, 0, 0)))
 
 
 def centroid_accumulate_native(X, labels, weights, sums, counts, k, chunk=None):
@@ -390,7 +389,7 @@ def centroid_reduce_native(X, labels, weights, sums, counts, k, ws: ReduceWorksp
 
 
 def bounds_filter_native(labels, ub, lb, shift, smax, delta, rlist, rcount, buf: EStepBuffers,
-                         cc=None, nf=0, fidx=None):
+                         cc=None, nf=0, fidx=None, records=None):
     """Hamerly pruning (csrc/estep_f32.hip bounds_filter_kernel): bounds
     moved by the centroid shifts; rows that can no longer be proven to keep
     their candidate set go to ``rlist`` (count in ``rcount``, on the device);
@@ -402,23 +401,25 @@ def bounds_filter_native(labels, ub, lb, shift, smax, delta, rlist, rcount, buf:
     ``cc`` [k nf + k] fp32 / ``nf``: the fastest centroids' Elkan distances
     (:func:`fast_centroids_native`; ``smax`` then excludes them).  The
     pass also zeroes ``buf.corr`` (the list-mode E-step that follows skips
-    its memset)."""
+    its memset).  ``records`` (:func:`multi_records`): rows with a current
+    gap record go to its list B instead."""
     n = labels.numel()
     assert ub.dtype == torch.float32 and lb.dtype == torch.float32 and rlist.numel() >= n
     assert shift.dtype == torch.float64 and smax.dtype == torch.float64
     assert buf.mflag is not None and buf.mflag.numel() >= n
-    rc = nat.native().bounds_filter(labels.data_ptr(), ub.data_ptr(), lb.data_ptr(),
-                                    shift.data_ptr(), smax.data_ptr(), n, float(delta),
-                                    rlist.data_ptr(), rcount.data_ptr(), buf.mflag.data_ptr(),
-                                    buf.multi_rows.data_ptr(), buf.counts[2:3].data_ptr(),
-                                    0 if cc is None else cc.data_ptr(),
-                                    0 if cc is None else fidx.data_ptr(),
-                                    int(nf if cc is not None else 0), int(shift.numel()),
-                                    nat.stream_handle(labels.device),
-                                    0 if buf.corr is None else buf.corr.data_ptr(),
-                                    buf.counts[7:8].data_ptr())
-    if rc:
-        raise RuntimeError(f"bounds_filter failed (hip error {rc})")
+    r = records
+    nat.native().bounds_filter(labels.data_ptr(), ub.data_ptr(), lb.data_ptr(),
+                               shift.data_ptr(), smax.data_ptr(), n, float(delta),
+                               rlist.data_ptr(), rcount.data_ptr(), buf.mflag.data_ptr(),
+                               buf.multi_rows.data_ptr(), buf.counts[2:3].data_ptr(),
+                               0 if cc is None else cc.data_ptr(),
+                               0 if cc is None else fidx.data_ptr(),
+                               int(nf if cc is not None else 0), int(shift.numel()),
+                               nat.stream_handle(labels.device),
+                               0 if buf.corr is None else buf.corr.data_ptr(),
+                               buf.counts[7:8].data_ptr(),
+                               *((0, 0, 0, 0, 0) if r is None
+                                 else (1, r.it_now, r.it_lo, r.rows_b, r.count_b)))
 
 
 def fast_centroids_native(shift, C, nf, idx, smax_rest, cc, shift_sq=None):
@@ -434,18 +435,37 @@ def fast_centroids_native(shift, C, nf, idx, smax_rest, cc, shift_sq=None):
     assert shift.numel() >= k and shift.is_contiguous()
     if shift_sq is not None:
         assert shift_sq.dtype == torch.float64 and shift_sq.is_contiguous() and shift_sq.numel() >= k
-    rc = nat.native().fast_centroids(shift.data_ptr(),
-                                     0 if shift_sq is None else shift_sq.data_ptr(), C.data_ptr(),
-                                     k, d, int(nf), idx.data_ptr(), smax_rest.data_ptr(),
-                                     cc.data_ptr(), nat.stream_handle(C.device))
-    if rc:
-        raise RuntimeError(f"fast_centroids failed (hip error {rc})")
+    nat.native().fast_centroids(shift.data_ptr(),
+                                0 if shift_sq is None else shift_sq.data_ptr(), C.data_ptr(),
+                                k, d, int(nf), idx.data_ptr(), smax_rest.data_ptr(),
+                                cc.data_ptr(), nat.stream_handle(C.device))
+
+
+class MultiRecords(NamedTuple):
+    """The gap-record arguments of ``sq_estep_x64`` (csrc/sq_api.h), in its
+    order: device addresses and integers (:func:`multi_records`)."""
+    rec: int
+    mflag: int
+    it_now: int
+    it_lo: int
+    ring: int
+    dsh: int
+    dq: int
+    dsh_stride: int
+    rows_b: int
+    count_b: int
+    n_done: int
+    rows_moved: int
+    count_moved: int
 
 
 def multi_records(rec=None, mflag=None, it_now=0, it_lo=0, dsh=None, dq=None, rows_b=None,
                   count_b=None, n_done=None, rows_moved=None, count_moved=None):
-    """Set (or clear, rec=None) the gap records used by this thread's next
-    certified E-steps (csrc/estep_f32.hip): the fp32 screen writes a row's
+    """The gap records of one certified E-step (csrc/estep_f32.hip) as a
+    :class:`MultiRecords` for the ``records=`` argument of
+    :func:`bounds_filter_native` and :func:`estep_x64_native` (None with
+    rec=None: records off).  It holds addresses, not the tensors: the caller
+    keeps those alive.  The fp32 screen writes a row's
     record with base ``it_now`` (mflag = 2 + base), the bounds filter lists
     rows whose base is in [it_lo, it_now - 1] in ``rows_b`` / ``count_b``,
     the gap screen moves their records by the shift operand of their base
@@ -455,22 +475,19 @@ def multi_records(rec=None, mflag=None, it_now=0, it_lo=0, dsh=None, dq=None, ro
     once each, the list-B rows whose label can have changed - those it
     resolved with a new argmin and those it forwarded to the multi list."""
     if rec is None:
-        nat.native().multi_records(0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0)
-        return
+        return None
     assert rec.dtype == torch.float32 and rec.shape[-1] == 8 and mflag.dtype == torch.int32
     assert dsh.dtype == torch.float16 and dq.dtype == torch.float32 and rows_b.dtype == torch.int64
     assert dsh.dim() == 3 and dq.shape[:2] == dsh.shape[:2] and dq.shape[2] == 8
     if rows_moved is not None:
         assert rows_moved.dtype == torch.int64 and rows_moved.numel() >= rows_b.numel()
         assert count_moved.dtype == torch.int32
-    rc = nat.native().multi_records(rec.data_ptr(), mflag.data_ptr(), int(it_now), int(it_lo),
-                                    int(dsh.shape[0]), dsh.data_ptr(), dq.data_ptr(),
-                                    int(dsh.stride(0)), rows_b.data_ptr(), count_b.data_ptr(),
-                                    0 if n_done is None else n_done.data_ptr(),
-                                    0 if rows_moved is None else rows_moved.data_ptr(),
-                                    0 if rows_moved is None else count_moved.data_ptr())
-    if rc:
-        raise RuntimeError(f"multi_records failed (hip error {rc})")
+    return MultiRecords(rec.data_ptr(), mflag.data_ptr(), int(it_now), int(it_lo),
+                        int(dsh.shape[0]), dsh.data_ptr(), dq.data_ptr(), int(dsh.stride(0)),
+                        rows_b.data_ptr(), count_b.data_ptr(),
+                        0 if n_done is None else n_done.data_ptr(),
+                        0 if rows_moved is None else rows_moved.data_ptr(),
+                        0 if rows_moved is None else count_moved.data_ptr())
 
 
 def shift_operand_native(C_prev, C_new, alpha, snap, dsh, dq, snew, valid):
@@ -483,12 +500,10 @@ def shift_operand_native(C_prev, C_new, alpha, snap, dsh, dq, snew, valid):
     assert C_prev.dtype == torch.float32 and C_new.dtype == torch.float32
     assert C_prev.stride() == C_new.stride() and C_new.stride(1) == 1
     assert tuple(snap.shape) == (ring, k, d_pad) and tuple(dq.shape) == (ring, k, 8)
-    rc = nat.native().shift_operand(C_prev.data_ptr(), C_new.data_ptr(), int(C_new.stride(0)), int(d),
-                                    int(d_pad), int(k), float(alpha), snap.data_ptr(), dsh.data_ptr(),
-                                    dq.data_ptr(), int(ring), int(snew), int(valid),
-                                    nat.stream_handle(C_new.device))
-    if rc:
-        raise RuntimeError(f"shift_operand failed (hip error {rc})")
+    nat.native().shift_operand(C_prev.data_ptr(), C_new.data_ptr(), int(C_new.stride(0)), int(d),
+                               int(d_pad), int(k), float(alpha), snap.data_ptr(), dsh.data_ptr(),
+                               dq.data_ptr(), int(ring), int(snew), int(valid),
+                               nat.stream_handle(C_new.device))
 
 
 def ensure_multi_buffers(buf: EStepBuffers, n, device, bounds=False):
@@ -529,30 +544,24 @@ def centroid_delta_native(X, labels, prev, sums, counts, qsum, k, ws: ReduceWork
                 rows, cnt = ent
                 assert rows.dtype == torch.int64 and cnt.dtype == torch.int32
                 lp += [rows.data_ptr(), cnt.data_ptr()]
-        rc = nat.native().centroid_delta_lists(X.data_ptr(), labels.data_ptr(), prev.data_ptr(),
-                                               sums.data_ptr(), counts.data_ptr(),
-                                               qsum.data_ptr(), n, d, k, ws.xexp, int(qexp),
-                                               ws.hist.data_ptr(), ws.cursor.data_ptr(),
-                                               perm2.data_ptr(), *lp, nat.stream_handle(X.device))
-        if rc:
-            raise RuntimeError(f"centroid_delta_lists failed (hip error {rc})")
+        nat.native().centroid_delta_lists(X.data_ptr(), labels.data_ptr(), prev.data_ptr(),
+                                          sums.data_ptr(), counts.data_ptr(),
+                                          qsum.data_ptr(), n, d, k, ws.xexp, int(qexp),
+                                          ws.hist.data_ptr(), ws.cursor.data_ptr(),
+                                          perm2.data_ptr(), *lp, nat.stream_handle(X.device))
         return
-    rc = nat.native().centroid_delta(X.data_ptr(), labels.data_ptr(), prev.data_ptr(),
-                                     sums.data_ptr(), counts.data_ptr(), qsum.data_ptr(), n, d, k,
-                                     ws.xexp, int(qexp), ws.hist.data_ptr(), ws.cursor.data_ptr(),
-                                     perm2.data_ptr(), nat.stream_handle(X.device))
-    if rc:
-        raise RuntimeError(f"centroid_delta failed (hip error {rc})")
+    nat.native().centroid_delta(X.data_ptr(), labels.data_ptr(), prev.data_ptr(),
+                                sums.data_ptr(), counts.data_ptr(), qsum.data_ptr(), n, d, k,
+                                ws.xexp, int(qexp), ws.hist.data_ptr(), ws.cursor.data_ptr(),
+                                perm2.data_ptr(), nat.stream_handle(X.device))
 
 
 def cluster_inertia_native(sums, counts, qsum, C, k, d, ws: ReduceWorkspace, qexp, part):
     """part[c] = Q_c - 2 c.S_c + n_c |c|^2 at the centroids C (fp32 [k][d])."""
     assert C.dtype == torch.float32 and C.is_contiguous() and tuple(C.shape) == (k, d)
-    rc = nat.native().cluster_inertia(sums.data_ptr(), counts.data_ptr(), qsum.data_ptr(),
-                                      C.data_ptr(), k, d, ws.xexp, int(qexp), part.data_ptr(),
-                                      nat.stream_handle(C.device))
-    if rc:
-        raise RuntimeError(f"cluster_inertia failed (hip error {rc})")
+    nat.native().cluster_inertia(sums.data_ptr(), counts.data_ptr(), qsum.data_ptr(),
+                                 C.data_ptr(), k, d, ws.xexp, int(qexp), part.data_ptr(),
+                                 nat.stream_handle(C.device))
 
 
 def mstep_stats_native(sums, counts, qsum, C, k, d, ws: ReduceWorkspace, qexp, corr, n, part,
@@ -567,12 +576,10 @@ def mstep_stats_native(sums, counts, qsum, C, k, d, ws: ReduceWorkspace, qexp, c
     assert C.dtype == torch.float32 and C.is_contiguous() and tuple(C.shape) == (k, d)
     assert part.numel() >= 512 + k and part.dtype == torch.float64
     assert corr.dtype == torch.float32 and corr.data_ptr() % 16 == 0
-    rc = nat.native().mstep_stats(sums.data_ptr(), counts.data_ptr(), qsum.data_ptr(),
-                                  C.data_ptr(), k, d, ws.xexp, int(qexp), corr.data_ptr(), int(n),
-                                  part.data_ptr(), inertia.data_ptr(), packed.data_ptr(),
-                                  nat.stream_handle(C.device))
-    if rc:
-        raise RuntimeError(f"mstep_stats failed (hip error {rc})")
+    nat.native().mstep_stats(sums.data_ptr(), counts.data_ptr(), qsum.data_ptr(),
+                             C.data_ptr(), k, d, ws.xexp, int(qexp), corr.data_ptr(), int(n),
+                             part.data_ptr(), inertia.data_ptr(), packed.data_ptr(),
+                             nat.stream_handle(C.device))
 
 
 def pack_stats_native(sums, counts, inertia, packed, k, d, ws: ReduceWorkspace, weighted=False):
@@ -755,11 +762,11 @@ def estep_f32_native(Xf, C_op, xn, C_master, k, delta, alpha, key: RngKey, row_o
     if not buf.ovf_clean:
         buf.ovf_count.zero_()
     buf.ovf_clean = False
-    rc = m.estep_f32(Xf.data_ptr(), C_op.data_ptr(), xn.data_ptr(), buf.labels.data_ptr(),
-                     buf.mind.data_ptr(), buf.ovf_rows.data_ptr(), buf.ovf_count.data_ptr(),
-                     buf.inertia_part.data_ptr(), int(buf.part_cap), buf.inertia.data_ptr(), n,
-                     d_pad, k_pad, float(alpha), float(delta), key.k0, key.k1, key.s0, key.s1,
-                     int(row_offset), buf.ovf_cap, st)
+    m.estep_f32(Xf.data_ptr(), C_op.data_ptr(), xn.data_ptr(), buf.labels.data_ptr(),
+                buf.mind.data_ptr(), buf.ovf_rows.data_ptr(), buf.ovf_count.data_ptr(),
+                buf.inertia_part.data_ptr(), int(buf.part_cap), buf.inertia.data_ptr(), n,
+                d_pad, k_pad, float(alpha), float(delta), key.k0, key.k1, key.s0, key.s1,
+                int(row_offset), buf.ovf_cap, st)
     rows_f64_native(Xf, C_master, buf.labels, buf.mind, delta, key, row_offset,
                     rows=(buf.ovf_rows, buf.ovf_count, buf.ovf_cap), stream=st)
     return buf.labels, buf.mind
@@ -792,18 +799,16 @@ def rows_f64_native(X, C, labels, mind, delta, key: RngKey, row_offset, rows=Non
     if grid is None:
         grid = max(1, min(groups, 1024 if rows is None else 512))
     st = stream if stream is not None else nat.stream_handle(X.device)
-    rc = nat.native().rows_f64(X.data_ptr(), int(ldx), C.data_ptr(), int(ldc), d, int(k), rptr,
-                               cnt_ptr, int(nd), int(cap), labels.data_ptr(), mind.data_ptr(),
-                               nat.ptr(corr), nat.ptr(ub), float(delta), key.k0, key.k1, key.s0,
-                               key.s1, int(row_offset), int(grid), st)
-    if rc:
-        raise RuntimeError(f"rows_f64 failed (hip error {rc})")
+    nat.native().rows_f64(X.data_ptr(), int(ldx), C.data_ptr(), int(ldc), d, int(k), rptr,
+                          cnt_ptr, int(nd), int(cap), labels.data_ptr(), mind.data_ptr(),
+                          nat.ptr(corr), nat.ptr(ub), float(delta), key.k0, key.k1, key.s0,
+                          key.s1, int(row_offset), int(grid), st)
     return labels, mind
 
 
 def estep_x64_native(Xh, Xf, C_op, C_pad, xn, cmax2, k, delta, alpha, key: RngKey, row_offset,
                      buf: EStepBuffers, stream=None, bounds=None, rows=None, zero_counts=True,
-                     screen=False, list_rs=0):
+                     screen=False, list_rs=0, records=None):
     """Certified E-step (``estep_x64_kernel``): one fp16 MFMA pass with a
     rigorous error bound, fp64 re-check of the candidate centroids, dense rows
     through the fp32-faithful 3-pass kernel.  Labels are the fp64 delta-band
@@ -820,7 +825,8 @@ def estep_x64_native(Xh, Xf, C_op, C_pad, xn, cmax2, k, delta, alpha, key: RngKe
     statistics), the fp64 re-check takes the rest.  ``list_rs``: row sets
     per wave of the list-mode sweep (0 = default 1: a short list finishes
     in one half-length sweep; 2 = the full sweep's tiling, for a list the
-    caller expects to hold nearly every row)."""
+    caller expects to hold nearly every row).  ``records``
+    (:func:`multi_records`): the gap records of this E-step (None: off)."""
     n, d_pad = Xf.shape
     k_pad = C_op.shape[0] * 64
     assert Xf.dtype == torch.float32 and Xf.is_contiguous() and d_pad in X64_D
@@ -843,9 +849,9 @@ def estep_x64_native(Xh, Xf, C_op, C_pad, xn, cmax2, k, delta, alpha, key: RngKe
     if d_pad <= 256 and os.environ.get("SQ_OVF2", "1") != "0":
         if buf.ovf2_rows is None or buf.ovf2_rows.numel() < n:
             buf.ovf2_rows = torch.empty(max(n, 1), dtype=torch.int64, device=Xf.device)
-        nat.native().set_overflow2(buf.ovf2_rows.data_ptr(), buf.counts[6:7].data_ptr())
+        ovf2 = (buf.ovf2_rows.data_ptr(), buf.counts[6:7].data_ptr())
     else:
-        nat.native().set_overflow2(0, 0)
+        ovf2 = (0, 0)
     nat.native().estep_x64(Xh.data_ptr(), Xf.data_ptr(), C_op.data_ptr(), C_pad.data_ptr(),
                            xn.data_ptr(), cmax2.data_ptr(), buf.labels.data_ptr(),
                            buf.mind.data_ptr(), buf.dense_rows.data_ptr(), buf.ovf_rows.data_ptr(),
@@ -859,7 +865,8 @@ def estep_x64_native(Xh, Xf, C_op, C_pad, xn, cmax2, k, delta, alpha, key: RngKe
                            buf.exact_flag.data_ptr() if screen else 0,
                            buf.counts.data_ptr(), buf.inertia_part.data_ptr(), int(buf.part_cap),
                            n, d_pad, d_pad, k, k_pad, float(alpha), float(delta), key.k0, key.k1,
-                           key.s0, key.s1, int(row_offset), st, int(list_rs))
+                           key.s0, key.s1, int(row_offset), int(list_rs), st,
+                           *(records if records is not None else (0,) * 13), *ovf2)
     return buf.labels, buf.mind
 
 
@@ -875,10 +882,8 @@ def sum_f32_native(v, n, part, out, extra=0):
     (deterministic); part >= 512 + extra doubles (the extra partials were
     written there by an earlier launch)."""
     assert part.numel() >= 512 + extra and part.dtype == torch.float64 and extra >= 0
-    rc = nat.native().sum_f32(v.data_ptr(), int(n), part.data_ptr(), int(extra), out.data_ptr(),
-                              nat.stream_handle(v.device))
-    if rc:
-        raise RuntimeError(f"sum_f32 failed (hip error {rc})")
+    nat.native().sum_f32(v.data_ptr(), int(n), part.data_ptr(), int(extra), out.data_ptr(),
+                         nat.stream_handle(v.device))
 
 
 # ------------------------------------------------- k-means++ (exact, pruned)
@@ -952,13 +957,13 @@ class KmppState:
         if self.n:
             c0 = c0.to(torch.float32).contiguous()
             q = self.prune and self.owns_q
-            _rc(self.m.kmpp_init(self.X.data_ptr(), self.ldx, self.d, self.n, c0.data_ptr(),
-                                 0 if self.w is None else self.w.data_ptr(),
-                                 self.closest.data_ptr(), self.nearest.data_ptr(), bmax.data_ptr(),
-                                 self.Xq.data_ptr() if q else 0, self.dq,
-                                 self.srow.data_ptr() if q else 0,
-                                 self.erow.data_ptr() if q else 0,
-                                 self.xq2.data_ptr() if q else 0, self.st), "kmpp_init")
+            self.m.kmpp_init(self.X.data_ptr(), self.ldx, self.d, self.n, c0.data_ptr(),
+                             0 if self.w is None else self.w.data_ptr(),
+                             self.closest.data_ptr(), self.nearest.data_ptr(), bmax.data_ptr(),
+                             self.Xq.data_ptr() if q else 0, self.dq,
+                             self.srow.data_ptr() if q else 0,
+                             self.erow.data_ptr() if q else 0,
+                             self.xq2.data_ptr() if q else 0, self.st)
         return bmax.max().reshape(1)
 
     def set_scale(self, max_pot, n_global):
@@ -969,10 +974,10 @@ class KmppState:
         self.scale = 1.0 if not mx > 0.0 else 2.0 ** math.floor(
             math.log2(2.0 ** 52 / (max(n_global, 1) * mx)))
         if self.n:
-            _rc(self.m.kmpp_block_totals(self.closest.data_ptr(),
-                                         0 if self.w is None else self.w.data_ptr(), self.n,
-                                         self.R, self.G, self.scale, self.block_tot.data_ptr(),
-                                         self.st), "kmpp_block_totals")
+            self.m.kmpp_block_totals(self.closest.data_ptr(),
+                                     0 if self.w is None else self.w.data_ptr(), self.n,
+                                     self.R, self.G, self.scale, self.block_tot.data_ptr(),
+                                     self.st)
         return self.block_tot.sum().reshape(1)
 
     def pick(self, vals, cands=None, cand_ids=None, row_offset=0, n_global=None):
@@ -989,15 +994,15 @@ class KmppState:
         if cands is not None:
             assert cands.dtype == torch.float32 and cands.is_contiguous()
             assert tuple(cands.shape) == (t, self.d) and cand_ids.dtype == torch.int64
-        _rc(self.m.kmpp_pick(self.block_tot.data_ptr(), self.G, self.R, self.n, vals.data_ptr(), t,
-                             self.closest.data_ptr(), self.mask[prev].data_ptr(),
-                             self.D[prev].data_ptr(),
-                             0 if self.best is None else self.best.data_ptr(),
-                             0 if self.w is None else self.w.data_ptr(), self.scale,
-                             self.pos.data_ptr(), self.X.data_ptr(), self.ldx, self.d,
-                             0 if cands is None else cands.data_ptr(),
-                             0 if cand_ids is None else cand_ids.data_ptr(), int(row_offset),
-                             int(self.n if n_global is None else n_global), self.st), "kmpp_pick")
+        self.m.kmpp_pick(self.block_tot.data_ptr(), self.G, self.R, self.n, vals.data_ptr(), t,
+                         self.closest.data_ptr(), self.mask[prev].data_ptr(),
+                         self.D[prev].data_ptr(),
+                         0 if self.best is None else self.best.data_ptr(),
+                         0 if self.w is None else self.w.data_ptr(), self.scale,
+                         self.pos.data_ptr(), self.X.data_ptr(), self.ldx, self.d,
+                         0 if cands is None else cands.data_ptr(),
+                         0 if cand_ids is None else cand_ids.data_ptr(), int(row_offset),
+                         int(self.n if n_global is None else n_global), self.st)
         return self.pos[:t].clone()
 
     def trials(self, cand, centers, c, reduce=True):
@@ -1010,30 +1015,29 @@ class KmppState:
         Cc = (centers if centers.dtype == torch.float32 else centers.float()).contiguous()
         m, st = self.m, self.st
         prev, cur = 1 - self.cur, self.cur
-        _rc(m.kmpp_cc(cand.data_ptr(), Cc.data_ptr(), int(c), self.d, t, self.cc.data_ptr(), self.k,
-                      self.cinfo.data_ptr(), self.candq.data_ptr(), self.dq, self.delta.data_ptr(),
-                      self.delta.numel(), self.counters.data_ptr(), st), "kmpp_cc")
+        m.kmpp_cc(cand.data_ptr(), Cc.data_ptr(), int(c), self.d, t, self.cc.data_ptr(), self.k,
+                  self.cinfo.data_ptr(), self.candq.data_ptr(), self.dq, self.delta.data_ptr(),
+                  self.delta.numel(), self.counters.data_ptr(), st)
         if self.n:
-            _rc(m.kmpp_screen(self.closest.data_ptr(), self.nearest.data_ptr(),
-                              self.mask[prev].data_ptr(), self.D[prev].data_ptr(),
-                              0 if self.best is None else self.best.data_ptr(), self.c_last,
-                              self.cc.data_ptr(), self.k, t, self.n, self.R, self.G,
-                              self.mask[cur].data_ptr(), self.surv.data_ptr(),
-                              self.exact.data_ptr(), self.scount.data_ptr(),
-                              self.ecount.data_ptr(), int(self.prune), st), "kmpp_screen")
+            m.kmpp_screen(self.closest.data_ptr(), self.nearest.data_ptr(),
+                          self.mask[prev].data_ptr(), self.D[prev].data_ptr(),
+                          0 if self.best is None else self.best.data_ptr(), self.c_last,
+                          self.cc.data_ptr(), self.k, t, self.n, self.R, self.G,
+                          self.mask[cur].data_ptr(), self.surv.data_ptr(),
+                          self.exact.data_ptr(), self.scount.data_ptr(),
+                          self.ecount.data_ptr(), int(self.prune), st)
             if self.prune:
-                _rc(m.kmpp_bound(self.Xq.data_ptr(), self.dq, self.srow.data_ptr(),
-                                 self.erow.data_ptr(), self.xq2.data_ptr(),
-                                 self.closest.data_ptr(), self.candq.data_ptr(),
-                                 self.cinfo.data_ptr(), t, self.d, self.n, self.R, self.G,
-                                 self.surv.data_ptr(), self.scount.data_ptr(),
-                                 self.exact.data_ptr(), self.ecount.data_ptr(), st),
-                    "kmpp_bound")
-            _rc(m.kmpp_exact(self.X.data_ptr(), self.ldx, self.d, self.n, t, cand.data_ptr(),
-                             self.closest.data_ptr(), 0 if self.w is None else self.w.data_ptr(),
-                             self.scale, self.exact.data_ptr(), self.ecount.data_ptr(),
-                             self.mask[cur].data_ptr(), self.D[cur].data_ptr(),
-                             self.delta.data_ptr(), self.R, self.G, st), "kmpp_exact")
+                m.kmpp_bound(self.Xq.data_ptr(), self.dq, self.srow.data_ptr(),
+                             self.erow.data_ptr(), self.xq2.data_ptr(),
+                             self.closest.data_ptr(), self.candq.data_ptr(),
+                             self.cinfo.data_ptr(), t, self.d, self.n, self.R, self.G,
+                             self.surv.data_ptr(), self.scount.data_ptr(),
+                             self.exact.data_ptr(), self.ecount.data_ptr(), st)
+            m.kmpp_exact(self.X.data_ptr(), self.ldx, self.d, self.n, t, cand.data_ptr(),
+                         self.closest.data_ptr(), 0 if self.w is None else self.w.data_ptr(),
+                         self.scale, self.exact.data_ptr(), self.ecount.data_ptr(),
+                         self.mask[cur].data_ptr(), self.D[cur].data_ptr(),
+                         self.delta.data_ptr(), self.R, self.G, st)
         return self.delta.sum(0) if reduce else None
 
     def apply(self, best, c):
@@ -1053,11 +1057,11 @@ class KmppState:
         sampling values; ``draws_next`` None: last centre)."""
         if self.best is None:
             self.best = torch.zeros(1, dtype=torch.int32, device=self.dev)
-        _rc(self.m.kmpp_finish(self.delta.data_ptr(), self.G, self.t, self.block_tot.data_ptr(),
-                               P.data_ptr(), 0 if draws_next is None else draws_next.data_ptr(),
-                               vals.data_ptr(), cands.data_ptr(), cand_ids.data_ptr(), self.d,
-                               centers.data_ptr(), ids.data_ptr(), int(c), self.best.data_ptr(),
-                               self.st), "kmpp_finish")
+        self.m.kmpp_finish(self.delta.data_ptr(), self.G, self.t, self.block_tot.data_ptr(),
+                           P.data_ptr(), 0 if draws_next is None else draws_next.data_ptr(),
+                           vals.data_ptr(), cands.data_ptr(), cand_ids.data_ptr(), self.d,
+                           centers.data_ptr(), ids.data_ptr(), int(c), self.best.data_ptr(),
+                           self.st)
         self.c_last = int(c)
         self.cur ^= 1
 
@@ -1162,7 +1166,7 @@ class KmppBatch:
         iap = ia.data_ptr()
 
         def run_op(op):
-            _rc(m.kmpp_batch(op, iap, stream), f"kmpp_batch op {op}")
+            m.kmpp_batch(op, iap, stream)
 
         cur, c_prev = 0, -1
         for c in range(1, k):
@@ -1182,11 +1186,6 @@ class KmppBatch:
             run_op(6)                       # winners, next sampling values
             c_prev, cur = c, cur ^ 1
         return self.centers, self.ids
-
-def _rc(rc, name):
-    if rc:
-        raise RuntimeError(f"{name} failed (hip error {rc})")
-
 
 # ------------------------------------------------ certified fp16 IPE screen
 # (csrc/ipe16.hip): the IPE E-step without a per-pair fp32 inner product.
@@ -1530,9 +1529,7 @@ class Ipe16:
         last = self.nchunks - 1
 
         def run(op):
-            rc = m.ipe16(op, iap, dap, st)
-            if rc:
-                raise RuntimeError(f"ipe16 op {op} failed (hip error {rc})")
+            m.ipe16(op, iap, dap, st)
 
         for c in range(self.nchunks):
             s, e = c * self.chunk, min(n, (c + 1) * self.chunk)

@@ -94,12 +94,10 @@ def xtx(A, B=None, mean_a=None, mean_b=None, out=None, accumulate=False):
     part = _part(dev, splits * npairs * TM * TN)
     ma, mb = _mean64(mean_a, dev), (None if sym else _mean64(mean_b, dev))
     Bt = A if sym else B
-    rc = nat.native().xtx(A.data_ptr(), nat.dtype_code(A), A.stride(0), nat.ptr(ma), da,
-                          Bt.data_ptr(), nat.dtype_code(Bt), Bt.stride(0), nat.ptr(mb), db, n,
-                          int(sym), splits, part.data_ptr(), out.data_ptr(), int(accumulate),
-                          nat.stream_handle(dev))
-    if rc:
-        raise RuntimeError(f"xtx failed (hip error {rc})")
+    nat.native().xtx(A.data_ptr(), nat.dtype_code(A), A.stride(0), nat.ptr(ma), da,
+                     Bt.data_ptr(), nat.dtype_code(Bt), Bt.stride(0), nat.ptr(mb), db, n,
+                     int(sym), splits, part.data_ptr(), out.data_ptr(), int(accumulate),
+                     nat.stream_handle(dev))
     return out
 
 
@@ -120,12 +118,10 @@ def xw(A, W, mean=None, upper=False, out_dtype=torch.float64, out=None):
     assert A.stride(1) == 1 and out.stride(1) == 1 and out.dtype in (torch.float32, torch.float64)
     Wd = W.to(device=dev, dtype=torch.float64).contiguous()
     m = _mean64(mean, dev)
-    rc = nat.native().xw(A.data_ptr(), nat.dtype_code(A), A.stride(0), nat.ptr(m), n, d,
-                         Wd.data_ptr(), Wd.stride(0), l, int(bool(upper)), out.data_ptr(),
-                         1 if out.dtype == torch.float64 else 0, out.stride(0),
-                         nat.stream_handle(dev))
-    if rc:
-        raise RuntimeError(f"xw failed (hip error {rc})")
+    nat.native().xw(A.data_ptr(), nat.dtype_code(A), A.stride(0), nat.ptr(m), n, d,
+                    Wd.data_ptr(), Wd.stride(0), l, int(bool(upper)), out.data_ptr(),
+                    1 if out.dtype == torch.float64 else 0, out.stride(0),
+                    nat.stream_handle(dev))
     return out
 
 
@@ -242,10 +238,8 @@ def col_moments_local(X):
         rpw = -(-n // wgs)
         wgs = -(-n // rpw)
         part = torch.empty((wgs, 2 * d), dtype=torch.float64, device=X.device)
-        rc = nat.native().col_moments(X.data_ptr(), nat.dtype_code(X), X.stride(0), n, d,
-                                      part.data_ptr(), wgs, nat.stream_handle(X.device))
-        if rc:
-            raise RuntimeError(f"col_moments failed (hip error {rc})")
+        nat.native().col_moments(X.data_ptr(), nat.dtype_code(X), X.stride(0), n, d,
+                                 part.data_ptr(), wgs, nat.stream_handle(X.device))
         tot = part.sum(0)
         return tot[:d], tot[d:]
     Xd = X.to(torch.float64)
@@ -281,12 +275,10 @@ def mu_power_sums_local(X, exponents, mean=None):
             b = float(exponents[1])
             if all(abs(float(e) - i * b) <= 1e-9 * max(1.0, i * b) for i, e in enumerate(exponents)):
                 qstep = b
-        rc = nat.native().mu_sums(X.data_ptr(), nat.dtype_code(X), X.stride(0), qd.data_ptr(), nq,
-                                  rowmax.data_ptr(), colsum.data_ptr(), part.data_ptr(), wgs,
-                                  nat.ptr(racc), n, d, nat.ptr(mu), qstep,
-                                  nat.stream_handle(X.device))
-        if rc:
-            raise RuntimeError(f"mu_sums failed (hip error {rc})")
+        nat.native().mu_sums(X.data_ptr(), nat.dtype_code(X), X.stride(0), qd.data_ptr(), nq,
+                             rowmax.data_ptr(), colsum.data_ptr(), part.data_ptr(), wgs,
+                             nat.ptr(racc), n, d, nat.ptr(mu), qstep,
+                             nat.stream_handle(X.device))
         return rowmax.double(), colsum.double()
     A = X.to(torch.float64)
     if mean is not None:

@@ -165,12 +165,10 @@ def multinomial_long(N, W, wrow, key: RngKey, sid, level=0):
             Wb[:, nfull] = W[:, nfull * _SEG:].clamp(min=0).sum(-1)
         Nseg = multinomial_long(N, Wb, wrow, key, sid, level + 1).reshape(-1).contiguous()
     cnt = torch.empty((B, m), dtype=torch.float64, device=dev)
-    rc = nat.native().mnom_segments(W.data_ptr(), W.stride(0), wrow.data_ptr(), m, B,
-                                    Nseg.data_ptr(), cnt.data_ptr(), cnt.stride(0), key.k0,
-                                    key.k1, key.s0, key.s1, sid.data_ptr(), int(level),
-                                    nat.stream_handle(dev))
-    if rc:
-        raise RuntimeError(f"mnom_segments failed (hip error {rc})")
+    nat.native().mnom_segments(W.data_ptr(), W.stride(0), wrow.data_ptr(), m, B,
+                               Nseg.data_ptr(), cnt.data_ptr(), cnt.stride(0), key.k0,
+                               key.k1, key.s0, key.s1, sid.data_ptr(), int(level),
+                               nat.stream_handle(dev))
     return cnt
 
 
@@ -326,14 +324,14 @@ def _tomography_rows_native(V, sched, delta, key: RngKey, norm, stop):
         return out
     if stop and T > 1:
         m.tomography(V.data_ptr(), r, d, sch.data_ptr(), T, 0, 0, err.data_ptr(), 0, ninf,
-                     key.k0, key.k1, key.s0, key.s1, 0, st)
+                     key.k0, key.k1, key.s0, key.s1, 0, st, 0.0)
         ok = err <= float(delta)
         first = torch.where(ok.any(1), ok.to(torch.int8).argmax(1),
                             torch.full((r,), T - 1, device=dev)).to(torch.int32).contiguous()
     else:
         first = torch.full((r,), T - 1, dtype=torch.int32, device=dev)
     m.tomography(V.data_ptr(), r, d, sch.data_ptr(), T, 1, first.data_ptr(), 0, out.data_ptr(),
-                 ninf, key.k0, key.k1, key.s0, key.s1, 0, st)
+                 ninf, key.k0, key.k1, key.s0, key.s1, 0, st, 0.0)
     return out
 
 

@@ -115,20 +115,16 @@ def test_bounds_filter_against_fp64_replica(n, k, nf, records):
         corr=torch.full((n,), 7.0, dtype=torch.float32, device=dev))
     rlist = torch.full((n,), -1, dtype=torch.int64, device=dev)
     rows_b = torch.full((n,), -1, dtype=torch.int64, device=dev)
-    try:
-        if records:
-            K.multi_records(torch.zeros((1, 8), dtype=torch.float32, device=dev), buf.mflag,
-                            IT_NOW, IT_LO, torch.zeros((RING, 1, 128), dtype=torch.float16,
-                                                       device=dev),
-                            torch.zeros((RING, 1, 8), dtype=torch.float32, device=dev), rows_b,
-                            buf.counts[5:6], buf.counts[4:5])
-        else:
-            K.multi_records(None)
-        K.bounds_filter_native(x.labels, ub, lb, x.shift, x.smax, DELTA, rlist, buf.counts[3:4],
-                               buf, cc=x.cc, nf=nf, fidx=x.fidx if nf else None)
-        torch.cuda.synchronize()
-    finally:
-        K.multi_records(None)
+    rec = None
+    if records:
+        rec = K.multi_records(torch.zeros((1, 8), dtype=torch.float32, device=dev), buf.mflag,
+                              IT_NOW, IT_LO, torch.zeros((RING, 1, 128), dtype=torch.float16,
+                                                         device=dev),
+                              torch.zeros((RING, 1, 8), dtype=torch.float32, device=dev), rows_b,
+                              buf.counts[5:6], buf.counts[4:5])
+    K.bounds_filter_native(x.labels, ub, lb, x.shift, x.smax, DELTA, rlist, buf.counts[3:4],
+                           buf, cc=x.cc, nf=nf, fidx=x.fidx if nf else None, records=rec)
+    torch.cuda.synchronize()
     near, holds = x.near, x.holds
     n_near = int(near.sum().item())
     print(f"n={n} k={k} nf={nf}: {int(holds.sum().item())} rows hold, {n_near} left out")

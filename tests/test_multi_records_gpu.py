@@ -23,7 +23,7 @@ def _data(n=60000, d=128, k=64, seed=0, spread=3.0):
     return X, C0
 
 
-def _run(monkeypatch, X, C0, on, iters=14, reset_at=None, p=0.0, delta=2.0, pipeline=False):
+def _engine(monkeypatch, X, C0, on, p=0.0, delta=2.0):
     monkeypatch.setenv("SQ_MULTI_RECORDS", "1" if on else "0")
     monkeypatch.setenv("SQ_ESTEP_BOUNDS", "1")
     monkeypatch.setenv("SQ_MSTEP_INCREMENTAL", "1")
@@ -34,6 +34,11 @@ def _run(monkeypatch, X, C0, on, iters=14, reset_at=None, p=0.0, delta=2.0, pipe
     assert eng.fast and eng.certified and eng.bounds and eng.incremental
     assert (eng.mrec is not None) == on
     eng.set_centers(torch.from_numpy(C0).cuda())
+    return eng
+
+
+def _run(monkeypatch, X, C0, on, iters=14, reset_at=None, p=0.0, delta=2.0, pipeline=False):
+    eng = _engine(monkeypatch, X, C0, on, p, delta)
     eng.pipeline = pipeline
     out, cert = [], 0
     for it in range(iters):
@@ -64,6 +69,31 @@ def test_records_on_off_bit_identical(monkeypatch, case):
         assert torch.equal(la, lb)
         assert torch.equal(Ca, Cb)
         assert sa == sb
+
+
+def test_interleaved_engines_match_their_own_runs(monkeypatch):
+    """Two engines on one thread, records on and records off, stepped
+    alternately: each reproduces the sequence it gives when run alone (the
+    records of one engine's E-step reach no other engine's launches)."""
+    X, C0 = _data()
+    iters = 14
+    alone = {on: _run(monkeypatch, X, C0, on, iters=iters)[0] for on in (True, False)}
+    engines = {on: _engine(monkeypatch, X, C0, on) for on in (True, False)}
+    cert = 0
+    for it in range(iters):
+        for on, eng in engines.items():
+            labels, sc = eng.step()
+            vals = sc.tolist()[:2]
+            torch.cuda.synchronize()
+            if on:
+                cert += int(eng.buf.counts[4].item())
+            la, Ca, sa = alone[on][it]
+            assert torch.equal(labels.cpu(), la), (on, it)
+            assert torch.equal(eng.centers().cpu(), Ca), (on, it)
+            assert vals == sa, (on, it)
+    for eng in engines.values():
+        eng.drop_pending()
+    assert cert > 0, "no row was resolved by the gap screen"
 
 
 def test_screen_wide_band_inertia_close_to_fp64_path(monkeypatch):
