@@ -200,7 +200,29 @@ static PyMethodDef methods[] = {
     {"device_arch", py_device_arch, METH_NOARGS, "(arch, CUs, LDS/CU, wave size)"},
     {nullptr, nullptr, 0, nullptr}};
 
+// splda.hip: the submodule ``_C.lda``.  Its format table is
+// tests/golden/native_formats_lda.json.
+static PyMethodDef lda_methods[] = {
+    SQ_FN(sp_lda_stage, VALUE, "doubles of gathered rows the LDA E-step stages per wave"),
+    SQ_FN(sp_lda_max_k, VALUE, "largest topic count of the LDA E-step"),
+    SQ_FN(sp_lda_estep, NOGIL, "CSR LDA variational E-step + fixed-point statistics"),
+    SQ_FN(sp_lda_bound, NOGIL, "CSR LDA per-document logsumexp term of the bound"),
+    {nullptr, nullptr, 0, nullptr}};
+
 static struct PyModuleDef moddef = {PyModuleDef_HEAD_INIT, "_C",
                                     "sq_learn_amd native HIP kernels (gfx950)", -1, methods};
+static struct PyModuleDef lda_moddef = {PyModuleDef_HEAD_INIT, "sq_learn_amd._C.lda",
+                                        "latent Dirichlet allocation kernels (splda.hip)", -1,
+                                        lda_methods};
 
-PyMODINIT_FUNC PyInit__C(void) { return PyModule_Create(&moddef); }
+PyMODINIT_FUNC PyInit__C(void) {
+  PyObject* m = PyModule_Create(&moddef);
+  if (!m) return nullptr;
+  PyObject* lda = PyModule_Create(&lda_moddef);
+  if (!lda || PyModule_AddObject(m, "lda", lda) < 0) {
+    Py_XDECREF(lda);
+    Py_DECREF(m);
+    return nullptr;
+  }
+  return m;
+}

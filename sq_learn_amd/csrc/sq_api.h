@@ -137,6 +137,18 @@ SQ_API int sq_sp_radius_mark(const void* qptr, const void* qidx, const void* qva
 SQ_API int sq_sp_radius_fill(const void* mask, const void* cs, long long m, long long n, int T,
                              long long total, void* out, void* stream);
 
+// splda.hip (sq_sp_lda_stage: the doubles of gathered rows a wave stages in LDS,
+// sq_sp_lda_max_k: the largest topic count; neither is an error code)
+SQ_API int sq_sp_lda_stage();
+SQ_API int sq_sp_lda_max_k();
+SQ_API int sq_sp_lda_estep(const void* indptr, const void* indices, const void* data,
+                           const void* tw_t, void* doc_topic, long long q0, long long m, int F,
+                           int k, double prior, int max_iters, double tol, void* iters, void* qhi,
+                           void* qlo, int hexp, int lexp, void* stream);
+SQ_API int sq_sp_lda_bound(const void* indptr, const void* indices, const void* data,
+                           const void* elog_theta, const void* elog_beta_t, long long q0,
+                           long long m, int F, int k, void* out, void* stream);
+
 // failure.hip
 SQ_API int sq_failure_inject(void* labels, long long n, int k, double p, int R, unsigned k0,
                              unsigned k1, unsigned s0, unsigned s1, unsigned t0, unsigned t1,

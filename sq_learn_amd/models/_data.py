@@ -215,6 +215,8 @@ class SparseData:
         self._segments = {}
         # tile pointer tables of ops/sparse_knn.py, by tile size
         self._knn_tables = {}
+        # (max |value|, largest column count) of ops/sparse_lda.py: the fixed-point bound
+        self._lda_bound = None
 
     @property
     def n_local(self):

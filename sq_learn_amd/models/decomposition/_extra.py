@@ -6,10 +6,10 @@ and ``LatentDirichletAllocation`` (``_lda.py`` + ``_online_lda_fast.pyx``,
 N28).
 
 Kernel matrices and eigendecompositions run in fp64 on the resolved
-device; the NMF coordinate-descent sweep and the LDA E-step are host C++
-(``csrc/host/decomposition_host.cpp``) - both are sequential per column /
-per document with tiny inner loops, where a GPU launch per step would cost
-more than the work.
+device; the NMF coordinate-descent sweep and the default LDA E-step are host
+C++ (``csrc/host/decomposition_host.cpp``).  ``LatentDirichletAllocation``
+with an explicit ``device`` runs its E-step and bound through
+``ops.sparse_lda`` instead (``_lda_device.py``).
 """
 
 import ctypes
@@ -842,7 +842,18 @@ def _as_csr(X):
 
 
 class LatentDirichletAllocation(TransformerMixin, BaseEstimator):
-    """Latent Dirichlet allocation with batch or online variational Bayes."""
+    """Latent Dirichlet allocation with batch or online variational Bayes.
+
+    ``device=None`` (the default) is the host path: the E-step of
+    ``csrc/host/decomposition_host.cpp``, whatever the global configuration
+    says.  An explicit ``device`` ("cpu", "cuda", "cuda:0") runs the E-step and
+    the bound through ``ops.sparse_lda`` (``csrc/splda.hip`` on a GPU) and the
+    M-step in torch on that device; the matrix goes there once per call as
+    CSR, online mini-batches are row ranges of it.  The random draws are the
+    host path's numpy draws in the same order, so a seeded device fit follows
+    the host fit to rounding.  On a GPU the stored values are fp32: integer
+    counts are exact, other weights (TF-IDF) are rounded to fp32.  The fitted
+    attributes are numpy arrays on every path."""
 
     def _more_tags(self):
         return {"requires_positive_X": True}
@@ -852,7 +863,7 @@ class LatentDirichletAllocation(TransformerMixin, BaseEstimator):
                  learning_method="batch", learning_decay=0.7, learning_offset=10.0, max_iter=10,
                  batch_size=128, evaluate_every=-1, total_samples=1e6, perp_tol=1e-1,
                  mean_change_tol=1e-3, max_doc_update_iter=100, n_jobs=None, verbose=0,
-                 random_state=None):
+                 random_state=None, device=None):
         self.n_components = n_components
         self.doc_topic_prior = doc_topic_prior
         self.topic_word_prior = topic_word_prior
@@ -869,6 +880,11 @@ class LatentDirichletAllocation(TransformerMixin, BaseEstimator):
         self.n_jobs = n_jobs
         self.verbose = verbose
         self.random_state = random_state
+        self.device = device
+
+    def _device_state(self, X):
+        from ._lda_device import DeviceLDA
+        return DeviceLDA(self, X)
 
     def _check(self, X, reset):
         X = _as_csr(X.detach().cpu().numpy() if hasattr(X, "detach") else X)
@@ -928,6 +944,8 @@ class LatentDirichletAllocation(TransformerMixin, BaseEstimator):
         X = self._check(X, reset=True)
         n = X.shape[0]
         self._init_latent_vars(X.shape[1])
+        if self.device is not None:
+            return self._fit_device(X)
         last = None
         for i in range(self.max_iter):
             if self.learning_method == "online":
@@ -946,11 +964,42 @@ class LatentDirichletAllocation(TransformerMixin, BaseEstimator):
         self.bound_ = self._perplexity_precomp(X, dt, False)
         return self
 
+    def _fit_device(self, X):
+        """``fit`` after the initialisation, on ``self.device``: the same loop
+        over row ranges of the one uploaded matrix."""
+        n = X.shape[0]
+        dl = self._device_state(X)
+        last = None
+        for i in range(self.max_iter):
+            if self.learning_method == "online":
+                for s in range(0, n, self.batch_size):
+                    dl.em_step(s, min(n, s + self.batch_size), n, False)
+            else:
+                dl.em_step(0, n, n, True)
+            if self.evaluate_every > 0 and (i + 1) % self.evaluate_every == 0:
+                dt, _ = dl.e_step(0, n, False, False)
+                bound = dl.perplexity(dt, False)
+                if last and abs(last - bound) < self.perp_tol:
+                    break
+                last = bound
+            self.n_iter_ += 1
+        dt, _ = dl.e_step(0, n, False, False)
+        self.bound_ = dl.perplexity(dt, False)
+        dl.store()
+        return self
+
     def partial_fit(self, X, y=None):
         first = not hasattr(self, "components_")
         X = self._check(X, reset=first)
         if first:
             self._init_latent_vars(X.shape[1])
+        if self.device is not None:
+            n = X.shape[0]
+            dl = self._device_state(X)
+            for s in range(0, n, self.batch_size):
+                dl.em_step(s, min(n, s + self.batch_size), self.total_samples, False)
+            dl.store()
+            return self
         for s in range(0, X.shape[0], self.batch_size):
             self._em_step(X[s:s + self.batch_size], self.total_samples, False)
         return self
@@ -961,7 +1010,10 @@ class LatentDirichletAllocation(TransformerMixin, BaseEstimator):
     def transform(self, X):
         check_is_fitted(self, "components_")
         X = self._check(X, reset=False)
-        dt = self._unnormalized_transform(X)
+        if self.device is not None:
+            dt = self._device_state(X).e_step(0, X.shape[0], False, False)[0].cpu().numpy()
+        else:
+            dt = self._unnormalized_transform(X)
         return dt / dt.sum(axis=1)[:, np.newaxis]
 
     def _approx_bound(self, X, dt, sub_sampling):
@@ -988,6 +1040,9 @@ class LatentDirichletAllocation(TransformerMixin, BaseEstimator):
     def score(self, X, y=None):
         check_is_fitted(self, "components_")
         X = self._check(X, reset=False)
+        if self.device is not None:
+            dl = self._device_state(X)
+            return dl.approx_bound(dl.e_step(0, X.shape[0], False, False)[0], False)
         return self._approx_bound(X, self._unnormalized_transform(X), False)
 
     def _perplexity_precomp(self, X, dt, sub_sampling):
@@ -998,6 +1053,9 @@ class LatentDirichletAllocation(TransformerMixin, BaseEstimator):
     def perplexity(self, X, sub_sampling=False):
         check_is_fitted(self, "components_")
         X = self._check(X, reset=False)
+        if self.device is not None:
+            dl = self._device_state(X)
+            return dl.perplexity(dl.e_step(0, X.shape[0], False, False)[0], sub_sampling)
         return self._perplexity_precomp(X, self._unnormalized_transform(X), sub_sampling)
 
 
