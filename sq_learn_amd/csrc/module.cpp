@@ -209,18 +209,42 @@ static PyMethodDef lda_methods[] = {
     SQ_FN(sp_lda_bound, NOGIL, "CSR LDA per-document logsumexp term of the bound"),
     {nullptr, nullptr, 0, nullptr}};
 
+// spnmf.hip: the submodule ``_C.nmf``.  Its format table is
+// tests/golden/native_formats_nmf.json.
+static PyMethodDef nmf_methods[] = {
+    SQ_FN(sp_nmf_stage, VALUE, "doubles of gathered rows the NMF ratio kernel stages per wave"),
+    SQ_FN(sp_nmf_stage_min_row, VALUE, "least doubles a staged entry counts as"),
+    SQ_FN(sp_nmf_max_k, VALUE, "largest component count of the NMF ratio kernel"),
+    SQ_FN(sp_nmf_wpb, VALUE, "waves per workgroup of the NMF ratio kernel at k components"),
+    SQ_FN(nmf_cd_max_k, VALUE, "largest component count of the NMF sweep"),
+    SQ_FN(nmf_cd_hht_k, VALUE, "component count up to which the NMF sweep keeps HHt in LDS"),
+    SQ_FN(nmf_cd_rows, VALUE, "rows per wave of the NMF sweep at k components"),
+    SQ_FN(sp_nmf_kl, NOGIL, "CSR NMF Kullback-Leibler ratio products and divergence term"),
+    SQ_FN(nmf_cd_sweep, NOGIL, "NMF coordinate-descent sweep over rows, in place"),
+    {nullptr, nullptr, 0, nullptr}};
+
 static struct PyModuleDef moddef = {PyModuleDef_HEAD_INIT, "_C",
                                     "sq_learn_amd native HIP kernels (gfx950)", -1, methods};
 static struct PyModuleDef lda_moddef = {PyModuleDef_HEAD_INIT, "sq_learn_amd._C.lda",
                                         "latent Dirichlet allocation kernels (splda.hip)", -1,
                                         lda_methods};
+static struct PyModuleDef nmf_moddef = {PyModuleDef_HEAD_INIT, "sq_learn_amd._C.nmf",
+                                        "non-negative matrix factorisation kernels (spnmf.hip)",
+                                        -1, nmf_methods};
+
+static bool add_submodule(PyObject* m, const char* name, PyModuleDef* def) {
+  PyObject* sub = PyModule_Create(def);
+  if (!sub || PyModule_AddObject(m, name, sub) < 0) {
+    Py_XDECREF(sub);
+    return false;
+  }
+  return true;
+}
 
 PyMODINIT_FUNC PyInit__C(void) {
   PyObject* m = PyModule_Create(&moddef);
   if (!m) return nullptr;
-  PyObject* lda = PyModule_Create(&lda_moddef);
-  if (!lda || PyModule_AddObject(m, "lda", lda) < 0) {
-    Py_XDECREF(lda);
+  if (!add_submodule(m, "lda", &lda_moddef) || !add_submodule(m, "nmf", &nmf_moddef)) {
     Py_DECREF(m);
     return nullptr;
   }

@@ -1,6 +1,7 @@
 // Wave-per-CSR-row helpers of the gather and scatter kernels: included by
-// csrc/spkmeans.hip (contiguous row ranges), csrc/spminibatch.hip (row lists)
-// and csrc/spmm.hip (row segments).  Placement rule: anything two sparse .hip
+// csrc/spkmeans.hip (contiguous row ranges), csrc/spminibatch.hip (row lists),
+// csrc/spmm.hip (row segments), csrc/splda.hip and csrc/spnmf.hip (one wave per
+// row, two phases).  Placement rule: anything two sparse .hip
 // files need lives here - the readlane broadcast of a row's (col, v) pairs,
 // the row-gather accumulation and the tile walk around it, the fixed-point
 // scatter, the per-row moments, the fixed-order sum of per-wave partials and
@@ -18,6 +19,12 @@ typedef double SpAcc __attribute__((ext_vector_type(SP_T)));
 SQ_DEV int bcast_i(int v, int q) { return __builtin_amdgcn_readlane(v, q); }
 SQ_DEV float bcast_f(float v, int q) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), q));
+}
+SQ_DEV double bcast_d(double v, int q) {
+  const long long b = __double_as_longlong(v);
+  const int lo = __builtin_amdgcn_readlane((int)b, q);
+  const int hi = __builtin_amdgcn_readlane((int)(b >> 32), q);
+  return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
 }
 SQ_DEV double wave_min_d(double v) {
 #pragma unroll

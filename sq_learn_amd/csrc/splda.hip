@@ -42,13 +42,6 @@ constexpr int SP_LDA_STAGE = 2048;   // doubles of gathered rows a wave stages i
 constexpr int SP_LDA_MAX_K = 4096;   // 3 LDS rows of k doubles + the stage, one wave
 constexpr double SP_LDA_EPS = 2.220446049250313e-16;
 
-SQ_DEV double bcast_d(double v, int q) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_readlane((int)b, q);
-  const int hi = __builtin_amdgcn_readlane((int)(b >> 32), q);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
-
 // the host file's digamma: recurrence up to x >= 6, then the asymptotic series.  The loop runs
 // at most 6 times: an argument that is not positive (NaN included) returns NaN at once, where
 // the host would walk up from it.

@@ -149,6 +149,25 @@ SQ_API int sq_sp_lda_bound(const void* indptr, const void* indices, const void* 
                            const void* elog_theta, const void* elog_beta_t, long long q0,
                            long long m, int F, int k, void* out, void* stream);
 
+// spnmf.hip (the first seven return a limit or a launch geometry, not an error code:
+// the doubles of gathered rows a wave stages in LDS and the least doubles a staged
+// entry counts as, the largest component count and the waves per workgroup of the
+// ratio kernel at k; the largest component count of the sweep, the k up to which it
+// keeps HHt in LDS and its rows per wave at k)
+SQ_API int sq_sp_nmf_stage();
+SQ_API int sq_sp_nmf_stage_min_row();
+SQ_API int sq_sp_nmf_max_k();
+SQ_API int sq_sp_nmf_wpb(int k);
+SQ_API int sq_nmf_cd_max_k();
+SQ_API int sq_nmf_cd_hht_k();
+SQ_API int sq_nmf_cd_rows(int k);
+SQ_API int sq_sp_nmf_kl(const void* indptr, const void* indices, const void* data, const void* P,
+                        const void* Q, long long q0, long long m, int cols, int k, double eps,
+                        void* num, void* div, void* stream);
+SQ_API int sq_nmf_cd_sweep(void* W, const void* HHt, const void* XHt, const void* perm,
+                           long long row0, long long m, int k, void* rowviol, void* violation,
+                           void* stream);
+
 // failure.hip
 SQ_API int sq_failure_inject(void* labels, long long n, int k, double p, int R, unsigned k0,
                              unsigned k1, unsigned s0, unsigned s1, unsigned t0, unsigned t1,

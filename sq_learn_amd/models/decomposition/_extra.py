@@ -6,10 +6,12 @@ and ``LatentDirichletAllocation`` (``_lda.py`` + ``_online_lda_fast.pyx``,
 N28).
 
 Kernel matrices and eigendecompositions run in fp64 on the resolved
-device; the NMF coordinate-descent sweep and the default LDA E-step are host
-C++ (``csrc/host/decomposition_host.cpp``).  ``LatentDirichletAllocation``
-with an explicit ``device`` runs its E-step and bound through
-``ops.sparse_lda`` instead (``_lda_device.py``).
+device; the default NMF coordinate-descent sweep and the default LDA E-step
+are host C++ (``csrc/host/decomposition_host.cpp``).
+``LatentDirichletAllocation`` with an explicit ``device`` runs its E-step and
+bound through ``ops.sparse_lda`` instead (``_lda_device.py``); ``NMF`` with an
+explicit ``device`` keeps scipy sparse input as CSR and runs its solvers
+through ``ops.sparse_nmf`` and ``ops.sparse_linalg`` (``_nmf_device.py``).
 """
 
 import ctypes
@@ -714,7 +716,23 @@ def _fit_mu(X, W, H, beta, max_iter, tol, l1W, l1H, l2W, l2H, update_H):
 
 class NMF(TransformerMixin, BaseEstimator):
     """Non-negative matrix factorisation X ~ W H (coordinate descent or
-    multiplicative updates; Frobenius / KL / IS / beta losses)."""
+    multiplicative updates; Frobenius / KL / IS / beta losses).
+
+    ``device=None`` (the default) is the host path: the input is densified,
+    the coordinate-descent sweep is ``csrc/host/decomposition_host.cpp``.  An
+    explicit ``device`` ("cpu", "cuda", "cuda:0") runs ``fit``,
+    ``fit_transform`` and ``transform`` on that device (``_nmf_device.py``): a
+    scipy sparse matrix of any format goes there once per call as canonical
+    CSR and is never densified, a dense one goes as fp64.  Solver 'cd' and
+    solver 'mu' with the Frobenius or the Kullback-Leibler loss run there; any
+    other ``beta_loss`` and more components than the kernels hold are refused.
+    Initialisation and the ``shuffle`` permutations are the host path's numpy
+    draws in the same order, so a seeded device fit follows the host fit to
+    rounding; the ``nndsvd*`` initialisations of a CSR matrix differ from the
+    densified host route by rounding too, because the sparse products of the
+    randomized SVD sum in another order.  On a GPU the stored values of a CSR
+    matrix are fp32: integer counts are exact, other weights (TF-IDF) are
+    rounded to fp32.  The fitted attributes are numpy arrays on every path."""
 
     def _more_tags(self):
         return {"requires_positive_X": True}
@@ -722,7 +740,7 @@ class NMF(TransformerMixin, BaseEstimator):
 
     def __init__(self, n_components=None, *, init="warn", solver="cd", beta_loss="frobenius",
                  tol=1e-4, max_iter=200, random_state=None, alpha=0.0, l1_ratio=0.0, verbose=0,
-                 shuffle=False, regularization="both"):
+                 shuffle=False, regularization="both", device=None):
         self.n_components = n_components
         self.init = init
         self.solver = solver
@@ -735,6 +753,7 @@ class NMF(TransformerMixin, BaseEstimator):
         self.verbose = verbose
         self.shuffle = shuffle
         self.regularization = regularization
+        self.device = device
 
     def _regs(self):
         aH = float(self.alpha) if self.regularization in ("both", "components") else 0.0
@@ -742,8 +761,24 @@ class NMF(TransformerMixin, BaseEstimator):
         r = self.l1_ratio
         return aW * r, aH * r, aW * (1.0 - r), aH * (1.0 - r)
 
-    def _fit_transform(self, X, W=None, H=None, update_H=True):
-        if (X < 0).any():
+    def _device_input(self, X):
+        """What the device path works on: canonical scipy CSR (never
+        densified) or a dense fp64 array."""
+        if not sp.issparse(X):
+            return _dense(X)
+        X = sp.csr_matrix(X, dtype=np.float64)
+        if not X.has_canonical_format:
+            X = X.copy()               # the caller's matrix is never mutated
+            X.sum_duplicates()
+            X.sort_indices()
+        return X
+
+    def _device_state(self, X):
+        from ._nmf_device import DeviceNMF
+        return DeviceNMF(self, X)
+
+    def _fit_transform(self, X, W=None, H=None, update_H=True, state=None):
+        if ((X.data if sp.issparse(X) else X) < 0).any():
             raise ValueError("Negative values in data passed to NMF (input X)")
         if self.solver not in ("cd", "mu"):
             raise ValueError("Invalid solver parameter: got %r instead of one of %r"
@@ -752,6 +787,10 @@ class NMF(TransformerMixin, BaseEstimator):
         if self.solver == "cd" and beta != 2:
             raise ValueError("Invalid beta_loss parameter: solver %r does not handle beta_loss = "
                              "%r" % (self.solver, self.beta_loss))
+        if self.device is not None and beta not in (1, 2):
+            raise ValueError("NMF with a device supports beta_loss 'frobenius' and "
+                             "'kullback-leibler' only: any other beta needs the dense "
+                             "(W H)^(beta - 1); got %r" % (self.beta_loss,))
         if self.solver == "mu" and self.init == "nndsvd":
             warnings.warn("The multiplicative update ('mu') solver cannot update zeros present "
                           "in the initialization, and so leads to poorer results when used "
@@ -766,6 +805,9 @@ class NMF(TransformerMixin, BaseEstimator):
             raise ValueError("Number of components must be a positive integer; got "
                              "(n_components=%r)" % nc)
         self._n_components = nc
+        if self.device is not None:
+            state = self._device_state(X) if state is None else state
+            state.check(nc, self.solver, beta)
         if self.init == "custom" and update_H:
             W, H = np.array(W, dtype=np.float64), np.array(H, dtype=np.float64)
         elif not update_H:
@@ -775,7 +817,9 @@ class NMF(TransformerMixin, BaseEstimator):
         else:
             W, H = _initialize_nmf(X, nc, init=self.init, random_state=self.random_state)
         l1W, l1H, l2W, l2H = self._regs()
-        if self.solver == "cd":
+        if self.device is not None:
+            W, H, n_iter = state.fit(W, H, beta, update_H)
+        elif self.solver == "cd":
             W, H, n_iter = _fit_cd(X, W, H, self.tol, self.max_iter, l1W, l1H, l2W, l2H, update_H,
                                    self.shuffle, self.random_state)
         else:
@@ -787,10 +831,18 @@ class NMF(TransformerMixin, BaseEstimator):
         return W, H, n_iter
 
     def fit_transform(self, X, y=None, W=None, H=None):
-        X = _dense(X)
-        self.n_features_in_ = X.shape[1]
-        W, H, n_iter = self._fit_transform(X, W=W, H=H)
-        self.reconstruction_err_ = _beta_divergence(X, W, H, self.beta_loss, square_root=True)
+        if self.device is not None:
+            X = self._device_input(X)
+            self.n_features_in_ = X.shape[1]
+            state = self._device_state(X)
+            W, H, n_iter = self._fit_transform(X, W=W, H=H, state=state)
+            self.reconstruction_err_ = state.reconstruction_err()
+        else:
+            X = _dense(X)
+            self.n_features_in_ = X.shape[1]
+            W, H, n_iter = self._fit_transform(X, W=W, H=H)
+            self.reconstruction_err_ = _beta_divergence(X, W, H, self.beta_loss,
+                                                        square_root=True)
         self.n_components_ = H.shape[0]
         self.components_ = H
         self.n_iter_ = n_iter
@@ -802,7 +854,7 @@ class NMF(TransformerMixin, BaseEstimator):
 
     def transform(self, X):
         check_is_fitted(self, "components_")
-        X = _dense(X)
+        X = _dense(X) if self.device is None else self._device_input(X)
         if X.shape[1] != self.n_features_in_:
             raise ValueError("X has %d features, but NMF is expecting %d features as input."
                              % (X.shape[1], self.n_features_in_))
@@ -816,14 +868,15 @@ class NMF(TransformerMixin, BaseEstimator):
 def non_negative_factorization(X, W=None, H=None, n_components=None, *, init="warn",
                                update_H=True, solver="cd", beta_loss="frobenius", tol=1e-4,
                                max_iter=200, alpha=0.0, l1_ratio=0.0, regularization=None,
-                               random_state=None, verbose=0, shuffle=False):
+                               random_state=None, verbose=0, shuffle=False, device=None):
     est = NMF(n_components=n_components, init=init, solver=solver, beta_loss=beta_loss, tol=tol,
               max_iter=max_iter, random_state=random_state, alpha=alpha, l1_ratio=l1_ratio,
               verbose=verbose, shuffle=shuffle,
-              regularization=regularization if regularization is not None else "both")
+              regularization=regularization if regularization is not None else "both",
+              device=device)
     if regularization is None:
         est.alpha = 0.0
-    X = _dense(X)
+    X = _dense(X) if device is None else est._device_input(X)
     return est._fit_transform(X, W=W, H=H, update_H=update_H)
 
 

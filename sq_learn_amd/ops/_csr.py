@@ -1,7 +1,7 @@
 """What every CSR sparse op module (``sparse_kmeans``, ``sparse_linalg``,
-``sparse_knn``, ``sparse_radius``, ``sparse_lda``) needs: the native-path test, the chunk
-iterator of the torch twins, the pointer triple of a launch, the row-list
-normaliser, the squared row norms and the cached transpose.  The five modules
+``sparse_knn``, ``sparse_radius``, ``sparse_lda``, ``sparse_nmf``) needs: the native-path
+test, the chunk iterator of the torch twins, the pointer triple of a launch, the row-list
+normaliser, the squared row norms and the cached transpose.  The six modules
 import from here and not from each other (``sparse_radius`` also uses the
 k-NN operand object and epilogue).
 """
