@@ -223,6 +223,15 @@ static PyMethodDef nmf_methods[] = {
     SQ_FN(nmf_cd_sweep, NOGIL, "NMF coordinate-descent sweep over rows, in place"),
     {nullptr, nullptr, 0, nullptr}};
 
+// splogit.hip: the submodule ``_C.logistic``.  Its format table is
+// tests/golden/native_formats_logistic.json.
+static PyMethodDef logistic_methods[] = {
+    SQ_FN(sp_logit_tile_classes, VALUE, "classes per pass of the multinomial loss kernel"),
+    SQ_FN(sp_logit_multi, NOGIL, "CSR multinomial logistic loss and residual"),
+    SQ_FN(sp_logit_bin, NOGIL, "CSR binary logistic loss and residual"),
+    SQ_FN(sp_matvec, NOGIL, "CSR x fp64 vector product over row segments"),
+    {nullptr, nullptr, 0, nullptr}};
+
 static struct PyModuleDef moddef = {PyModuleDef_HEAD_INIT, "_C",
                                     "sq_learn_amd native HIP kernels (gfx950)", -1, methods};
 static struct PyModuleDef lda_moddef = {PyModuleDef_HEAD_INIT, "sq_learn_amd._C.lda",
@@ -231,6 +240,9 @@ static struct PyModuleDef lda_moddef = {PyModuleDef_HEAD_INIT, "sq_learn_amd._C.
 static struct PyModuleDef nmf_moddef = {PyModuleDef_HEAD_INIT, "sq_learn_amd._C.nmf",
                                         "non-negative matrix factorisation kernels (spnmf.hip)",
                                         -1, nmf_methods};
+static struct PyModuleDef logistic_moddef = {PyModuleDef_HEAD_INIT, "sq_learn_amd._C.logistic",
+                                             "logistic-regression loss kernels (splogit.hip)", -1,
+                                             logistic_methods};
 
 static bool add_submodule(PyObject* m, const char* name, PyModuleDef* def) {
   PyObject* sub = PyModule_Create(def);
@@ -244,7 +256,8 @@ static bool add_submodule(PyObject* m, const char* name, PyModuleDef* def) {
 PyMODINIT_FUNC PyInit__C(void) {
   PyObject* m = PyModule_Create(&moddef);
   if (!m) return nullptr;
-  if (!add_submodule(m, "lda", &lda_moddef) || !add_submodule(m, "nmf", &nmf_moddef)) {
+  if (!add_submodule(m, "lda", &lda_moddef) || !add_submodule(m, "nmf", &nmf_moddef) ||
+      !add_submodule(m, "logistic", &logistic_moddef)) {
     Py_DECREF(m);
     return nullptr;
   }

@@ -1,7 +1,7 @@
 // Wave-per-CSR-row helpers of the gather and scatter kernels: included by
 // csrc/spkmeans.hip (contiguous row ranges), csrc/spminibatch.hip (row lists),
-// csrc/spmm.hip (row segments), csrc/splda.hip and csrc/spnmf.hip (one wave per
-// row, two phases).  Placement rule: anything two sparse .hip
+// csrc/spmm.hip (row segments), csrc/splda.hip, csrc/spnmf.hip and
+// csrc/splogit.hip (one wave per row, two phases).  Placement rule: anything two sparse .hip
 // files need lives here - the readlane broadcast of a row's (col, v) pairs,
 // the row-gather accumulation and the tile walk around it, the fixed-point
 // scatter, the per-row moments, the fixed-order sum of per-wave partials and

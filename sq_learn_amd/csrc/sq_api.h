@@ -168,6 +168,22 @@ SQ_API int sq_nmf_cd_sweep(void* W, const void* HHt, const void* XHt, const void
                            long long row0, long long m, int k, void* rowviol, void* violation,
                            void* stream);
 
+// splogit.hip (sq_sp_logit_tile_classes: the classes one pass over a row covers, not
+// an error code; b of sq_sp_logit_bin: the intercept, a host value)
+SQ_API int sq_sp_logit_tile_classes();
+SQ_API int sq_sp_logit_multi(const void* indptr, const void* indices, const void* data,
+                             const void* Wt, long long ldw, const void* bias, const void* lab,
+                             const void* sw, long long n, int K, void* R, void* rowloss,
+                             void* loss, void* stream);
+SQ_API int sq_sp_logit_bin(const void* indptr, const void* indices, const void* data,
+                           const void* w, double b, const void* lab, const void* sw, long long n,
+                           int d, void* r, void* rowloss, void* loss, void* stream);
+SQ_API int sq_sp_matvec(const void* indptr, const void* indices, const void* data,
+                        const void* seg_row, const void* seg_start, const void* seg_dst,
+                        long long nseg, int seg, const void* long_row, const void* long_ptr,
+                        long long nlong, const void* x, int cols, void* y, void* scratch,
+                        void* stream);
+
 // failure.hip
 SQ_API int sq_failure_inject(void* labels, long long n, int k, double p, int R, unsigned k0,
                              unsigned k1, unsigned s0, unsigned s1, unsigned t0, unsigned t1,

@@ -14,7 +14,12 @@ coefficients and n_iter_ as the reference's; 'newton-cg' solves the same
 strictly convex problem with the L-BFGS driver; liblinear's l1 penalty
 uses an accelerated proximal gradient
 (FISTA with backtracking) on the device, minimising
-sum_i w_i loss_i + (1 - r) / (2C) ||W||^2 + r / C ||W||_1."""
+sum_i w_i loss_i + (1 - r) / (2C) ||W||^2 + r / C ||W||_1.
+
+With an explicit ``device``, scipy sparse rows stay CSR on the device wherever
+the device objective is the solver (lbfgs, newton-cg, the l1 branch):
+``_SparseObjective`` on ``ops/sparse_logistic.py`` (``csrc/splogit.hip`` on a
+GPU), and ``decision_function`` takes sparse X without densifying it."""
 
 import numbers
 import warnings
@@ -25,7 +30,12 @@ from scipy import optimize
 
 from ...base import ClassifierMixin
 from ...exceptions import ConvergenceWarning
+from ...ops import sparse_logistic as SL
+from ...ops._csr import csr_transpose
+from ...ops.sparse_linalg import sp_xw
 from ...runtime.device import resolve_device
+from ...utils.validation import check_is_fitted
+from .._data import as_sparse_data
 from ._base import LinearClassifierMixin, SparseCoefMixin, _as_dense64, _check_sample_weight
 from ...base import BaseEstimator
 
@@ -96,6 +106,52 @@ class _Objective:
             gW = self.X.T @ z0 + alpha * W
             g = torch.cat([gW, z0.sum().reshape(1)]) if self.fi else gW
         return float(loss), g.reshape(-1).cpu().numpy()
+
+
+class _SparseObjective:
+    """``_Objective`` on CSR rows that stay sparse on the device: the loss and
+    the residual are one op of ``ops/sparse_logistic.py`` per evaluation (on a
+    GPU the kernels of ``csrc/splogit.hip``), the gradient a product with the
+    cached transpose.  ``lab``: the class index of every row (multinomial) or
+    its 0 / 1 membership (one binary problem).  The l2 term is added on the
+    host."""
+
+    def __init__(self, sd, lab, n_classes, sw, alpha, fit_intercept, multinomial):
+        self.sd = sd
+        self.dev = sd.device
+        self.lab = torch.as_tensor(np.asarray(lab, dtype=np.int32)).to(self.dev)
+        self.sw = torch.as_tensor(np.asarray(sw, dtype=np.float64)).to(self.dev)
+        self.alpha = alpha
+        self.fi = fit_intercept
+        self.multi = multinomial
+        self.nf = sd.shape[1]
+        self.T = np.empty((0, n_classes))     # _fista reads T.shape[1]
+
+    def smooth(self, w, alpha=None):
+        """(loss, grad) of sum sw * logloss + alpha/2 ||W||^2 (intercept free)."""
+        alpha = self.alpha if alpha is None else alpha
+        w = np.asarray(w, dtype=np.float64)
+        pen = w.copy()
+        if self.multi:
+            W = w.reshape(self.T.shape[1], -1)
+            if self.fi:
+                pen.reshape(W.shape)[:, -1] = 0.0
+            b = W[:, -1] if self.fi else np.zeros(W.shape[0])
+            loss, R = SL.logit_multi(self.sd, SL.transposed_weights(W[:, :self.nf], self.dev),
+                                     np.ascontiguousarray(b), self.lab, self.sw)
+            g = SL.sp_xtr(self.sd, R).T
+            if self.fi:
+                g = torch.cat([g, R.sum(0)[:, None]], 1)
+        else:
+            if self.fi:
+                pen[-1] = 0.0
+            loss, r = SL.logit_bin(self.sd, np.ascontiguousarray(w[:self.nf]),
+                                   w[-1] if self.fi else 0.0, self.lab, self.sw)
+            g = SL.sp_matvec(csr_transpose(self.sd), r)
+            if self.fi:
+                g = torch.cat([g, r.sum().reshape(1)])
+        out = torch.cat([g.reshape(-1), loss.reshape(1)]).cpu().numpy()   # one copy to the host
+        return float(out[-1]) + 0.5 * alpha * float(pen @ pen), out[:-1] + alpha * pen
 
 
 def _lbfgs(obj, w0, tol, max_iter, verbose=0):
@@ -195,28 +251,37 @@ class LogisticRegression(LinearClassifierMixin, SparseCoefMixin, BaseEstimator):
                              % self.max_iter)
         import scipy.sparse as _sp
         self._sparse_fit = _sp.issparse(X)
-        X = _as_dense64(X).astype(np.float64)
+        C = np.inf if penalty == "none" else self.C
+        r = 1.0 if penalty == "l1" else (self.l1_ratio if penalty == "elasticnet" else 0.0)
+        alpha = 0.0 if C == np.inf else (1.0 - r) / C
+        l1 = 0.0 if C == np.inf else r / C
+        tron = self.solver == "liblinear" and l1 == 0 and np.isfinite(C)
+        dev = resolve_device(self.device)
+        # sparse rows stay CSR on an explicit device wherever the device objective is the solver
+        sd = None
+        if self._sparse_fit and self.device is not None and not tron \
+                and self.solver not in ("sag", "saga"):
+            sd = as_sparse_data(X, dev)
+            n_samples, n_features = sd.shape
+        else:
+            X = _as_dense64(X).astype(np.float64)
+            n_samples, n_features = X.shape
         y = np.asarray(y)
         if y.ndim != 1:
             y = y.ravel()
-        self.n_features_in_ = X.shape[1]
+        self.n_features_in_ = n_features
         self.classes_ = np.unique(y)
         n_classes = len(self.classes_)
         if n_classes < 2:
             raise ValueError("This solver needs samples of at least 2 classes in the data, but "
                              "the data contains only one class: %r" % self.classes_[0])
         multi = _check_multi_class(self.multi_class, self.solver, n_classes)
-        C = np.inf if penalty == "none" else self.C
-        r = 1.0 if penalty == "l1" else (self.l1_ratio if penalty == "elasticnet" else 0.0)
-        alpha = 0.0 if C == np.inf else (1.0 - r) / C
-        l1 = 0.0 if C == np.inf else r / C
-        sw = _check_sample_weight(sample_weight, X.shape[0])
-        sw = np.ones(X.shape[0]) if sw is None else sw.copy()
+        sw = _check_sample_weight(sample_weight, n_samples)
+        sw = np.ones(n_samples) if sw is None else sw.copy()
         cw = _class_weights(self.class_weight, self.classes_, y)
         sw_raw = sw
         sw = sw * cw[np.searchsorted(self.classes_, y)]
-        dev = resolve_device(self.device)
-        nf1 = X.shape[1] + int(self.fit_intercept)
+        nf1 = n_features + int(self.fit_intercept)
         warm = getattr(self, "coef_", None) if self.warm_start else None
 
         def solve(obj, w0):
@@ -227,13 +292,17 @@ class LogisticRegression(LinearClassifierMixin, SparseCoefMixin, BaseEstimator):
         if self.solver in ("sag", "saga"):
             W = self._fit_sag(X, y, sw, alpha, l1, multi, warm)
         elif multi == "multinomial":
-            Y = (y[:, None] == self.classes_[None, :]).astype(np.float64)
             w0 = np.zeros((n_classes, nf1))
             if warm is not None:
                 w0[-warm.shape[0]:, :warm.shape[1]] = warm
                 if self.fit_intercept:
                     w0[-warm.shape[0]:, -1] = self.intercept_
-            obj = _Objective(X, Y, sw, alpha, self.fit_intercept, True, dev)
+            if sd is not None:
+                obj = _SparseObjective(sd, np.searchsorted(self.classes_, y), n_classes, sw,
+                                       alpha, self.fit_intercept, True)
+            else:
+                Y = (y[:, None] == self.classes_[None, :]).astype(np.float64)
+                obj = _Objective(X, Y, sw, alpha, self.fit_intercept, True, dev)
             w, it = solve(obj, w0.ravel())
             W = w.reshape(n_classes, nf1)
             if n_classes == 2:
@@ -249,7 +318,7 @@ class LogisticRegression(LinearClassifierMixin, SparseCoefMixin, BaseEstimator):
                     w0[:warm.shape[1]] = warm[k]
                     if self.fit_intercept:
                         w0[-1] = self.intercept_[k]
-                if self.solver == "liblinear" and l1 == 0 and np.isfinite(C):
+                if tron:
                     # L2R_LR (liblinear type 0): TRON on the augmented rows,
                     # the bias column scaled by intercept_scaling and
                     # penalised like the weights (reference _base.py
@@ -261,7 +330,10 @@ class LogisticRegression(LinearClassifierMixin, SparseCoefMixin, BaseEstimator):
                         sw_raw * C * np.where(y == c, cw[k], 1.0)
                     w, it = self._liblinear_l2(X, t, Cv, w0)
                 else:
-                    obj = _Objective(X, t, sw, alpha, self.fit_intercept, False, dev)
+                    if sd is not None:
+                        obj = _SparseObjective(sd, y == c, 2, sw, alpha, self.fit_intercept, False)
+                    else:
+                        obj = _Objective(X, t, sw, alpha, self.fit_intercept, False, dev)
                     w, it = solve(obj, w0)
                 rows.append(w)
                 its.append(it)
@@ -269,7 +341,7 @@ class LogisticRegression(LinearClassifierMixin, SparseCoefMixin, BaseEstimator):
             self.n_iter_ = np.asarray(its, dtype=np.int32)
         if self.fit_intercept:
             self.intercept_ = W[:, -1].copy()
-            if self.solver == "liblinear" and l1 == 0 and np.isfinite(C):
+            if tron:
                 self.intercept_ *= self.intercept_scaling
             self.coef_ = W[:, :-1].copy()
         else:
@@ -331,6 +403,22 @@ class LogisticRegression(LinearClassifierMixin, SparseCoefMixin, BaseEstimator):
             its.append(it)
         self.n_iter_ = np.asarray(its, dtype=np.int32)
         return np.vstack(rows)
+
+    def decision_function(self, X):
+        """Sparse X on an estimator with an explicit device stays CSR: the
+        scores are ``sp_matvec`` for one coefficient row, ``sp_xw`` for more."""
+        import scipy.sparse as _sp
+        if not _sp.issparse(X) or self.device is None:
+            return super().decision_function(X)
+        check_is_fitted(self)
+        n_features = self.coef_.shape[1]
+        if X.shape[1] != n_features:
+            raise ValueError("X has %d features per sample; expecting %d" % (X.shape[1], n_features))
+        sd = as_sparse_data(X, resolve_device(self.device))
+        if self.coef_.shape[0] == 1:
+            return SL.sp_matvec(sd, self.coef_[0]).cpu().numpy() + self.intercept_[0]
+        coef_t = torch.as_tensor(np.ascontiguousarray(self.coef_.T), dtype=torch.float64)
+        return sp_xw(sd, coef_t).cpu().numpy() + self.intercept_
 
     def predict_proba(self, X):
         ovr = (self.multi_class == "ovr" or
