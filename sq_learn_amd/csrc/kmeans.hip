@@ -2022,10 +2022,17 @@ int sq_centroid_reduce(const void* X, int xdtype, const void* labels, const void
                        void* ws_hist, void* ws_cursor, void* ws_perm, void* mind,
                        const void* Cold, void* stream) {
   if (mind && (xdtype != 0 || d > 256 || d % 4 != 0 || !Cold)) return (int)hipErrorInvalidValue;
-  if (n <= 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (n <= 0) {
+    // an empty shard: no histogram launch zeroes the outputs, and they are
+    // still overwritten (its zeros enter the all-reduce)
+    if (k <= 0 || d <= 0) return 0;
+    hipError_t e = hipMemsetAsync(sums, 0, (size_t)k * d * sizeof(double), st);
+    if (e == hipSuccess) e = hipMemsetAsync(counts, 0, (size_t)k * sizeof(double), st);
+    return (int)e;
+  }
   if (d % 4 != 0 || k > 16384 || n > 2147483647LL) return (int)hipErrorInvalidValue;
   if (xexp < -120 || xexp > 120 || wexp < -120 || wexp > 120) return (int)hipErrorInvalidValue;
-  hipStream_t st = (hipStream_t)stream;
   unsigned chunks = (unsigned)((n + kHistChunk - 1) / kHistChunk);
   // ws_hist is all-zero on entry (zeroed at allocation, re-zeroed by the scan)
   hipLaunchKernelGGL(label_hist_kernel, dim3(chunks), dim3(256), (size_t)k * 4, st,

@@ -370,7 +370,8 @@ class ReduceWorkspace:
 def centroid_reduce_native(X, labels, weights, sums, counts, k, ws: ReduceWorkspace, mind=None,
                            C_old=None):
     """sums[l] = sum_{i: label_i = l} w_i x_i, counts[l] = sum w_i (GPU; the
-    outputs are overwritten - zeroed inside the histogram launch),
+    outputs are overwritten - zeroed inside the histogram launch, or by a
+    memset when the shard is empty),
     in units of the quanta 2^ws.xexp / 2^ws.wexp (exact integer-valued fp64,
     order-independent: bit-reproducible).  ``pack_stats_native`` rescales."""
     n, d = X.shape

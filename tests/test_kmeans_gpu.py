@@ -144,10 +144,11 @@ def test_centroid_accumulate(cuda):
                                      (torch.bfloat16, 512)])
 def test_centroid_reduce(cuda, dtype, d):
     n, k = 70001, 1000
-    X = torch.randn(n, d, dtype=torch.float32, device=cuda).to(dtype)
-    lab = torch.randint(0, k, (n,), dtype=torch.int32, device=cuda)
+    g = torch.Generator(device=cuda).manual_seed(5)
+    X = torch.randn(n, d, dtype=torch.float32, device=cuda, generator=g).to(dtype)
+    lab = torch.randint(0, k, (n,), dtype=torch.int32, device=cuda, generator=g)
     lab[:5000] = 3  # a big cluster
-    w = torch.rand(n, dtype=torch.float32, device=cuda)
+    w = torch.rand(n, dtype=torch.float32, device=cuda, generator=g)
     packed = torch.zeros(k * d + k + 1, dtype=torch.float64, device=cuda)
     for weights in (None, w):
         ws = K.ReduceWorkspace(n, k, cuda).set_scale(float(X.float().abs().max()), n,
