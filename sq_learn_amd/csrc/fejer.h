@@ -40,29 +40,71 @@ struct WordStream {
 // computed once; sample() then costs the walk (plus rare tail rejections).
 // fejer_sample() below = FejerLaw(omega, M).sample(ws): identical words and
 // results to the CPU twin (ops/random.py fejer_sample_torch).
+//
+// The walk is fp32.  Two things keep it sound at every phase and M <= 2^40:
+//  * Scale.  With 2^e <= M < 2^(e+1) the walk carries 2^e sin(.) instead of
+//    sin(.) and 2^(2e) / M^2 instead of 1 / M^2.  Powers of two commute with
+//    rounding, so every term has the mantissa the unscaled walk gives, but
+//    sin^2(pi phi / M) and sin^2(pi phi) / M^2 no longer underflow (unscaled,
+//    M = 2^40 with phi = 1e-12 gave 0 / 0).  Below pi phi < 2^-50 the bin
+//    l = 0 holds 1 - O(2^-100) of the mass and is taken outright.
+//  * l = +1.  sin(alpha - beta) = sin(pi (1 - phi) / M) by angle subtraction
+//    loses a factor (1 + phi) / (1 - phi) of its precision.  For phi <= 1/2
+//    that is at most 3, the same as every |l| >= 2 ((t + phi) / (t - phi) <= 3),
+//    and the subtraction stays.  For phi > 1/2, where this bin takes most of
+//    the mass, the sine comes from its own angle gamma = pi (1 - phi) / M,
+//    formed in fp64; sin^2(pi phi) is taken as sin^2(pi (1 - phi)) there too
+//    (1 - phi is exact, pi phi near pi is not).
 struct FejerLaw {
   double omega, phi, Md;
   long long M, base;
-  float s, sa, ca, sb, cb, inv_m2;
+  // s = sin^2(pi phi); sin/cos of alpha = pi / M and beta = pi phi / M with
+  // sb = 2^e sin(beta), sa_up = 2^e sin(alpha), sa_dn = 2^-e sin(alpha);
+  // s1 = 2^e sin(gamma) when phi > 1/2, else 0; inv_m2 = 2^(2e) / M^2
+  float s, sa_up, sa_dn, ca, sb, cb, s1, inv_m2;
   SQ_DEV FejerLaw(double omega_, long long M_) : omega(omega_), M(M_) {
     const double PI = 3.14159265358979323846;
     const double fl = floor(omega);
     phi = omega - fl;
     Md = (double)M;
     base = (long long)fl;
-    s = 0.f; sa = ca = sb = cb = inv_m2 = 0.f;
+    s = 0.f; sa_up = sa_dn = ca = sb = cb = s1 = inv_m2 = 0.f;
     if (phi == 0.0) return;
-    s = (float)sin(PI * phi);
+    const bool upper = phi > 0.5;
+    s = (float)sin(PI * (upper ? 1.0 - phi : phi));
     s = s * s;
     if (M <= kFejerSmallM) return;
+    if (PI * phi < 0x1p-50) {   // walk_term(sb) == 1: every draw stops at l = 0
+      s = sb = cb = inv_m2 = 1.f;
+      return;
+    }
+    const int e = 63 - __builtin_clzll((unsigned long long)M);
+    const float up = ldexpf(1.f, e), dn = ldexpf(1.f, -e);
     const float alpha = (float)(PI / Md);
     const float beta = (float)(PI * phi / Md);
+    float sa;
     __sincosf(beta, &sb, &cb);
     __sincosf(alpha, &sa, &ca);
-    inv_m2 = (float)(1.0 / (Md * Md));
+    sb *= up;
+    sa_up = sa * up;
+    sa_dn = sa * dn;
+    if (upper) s1 = __sinf((float)(PI * (1.0 - phi) / Md)) * up;
+    inv_m2 = (float)(1.0 / (Md * Md)) * up * up;
   }
-  // pmf of the walk offset l (bin base + l) given sin(l alpha - beta)
+  // pmf of the walk offset l (bin base + l) given 2^e sin(l alpha - beta)
   SQ_DEV float walk_term(float sn) const { return s * inv_m2 / (sn * sn); }
+  // (st, ct) = (2^e sin, cos)(t alpha) -> the same of (t + 1) alpha
+  SQ_DEV void walk_step(float& st, float& ct) const {
+    const float nst = st * ca + ct * sa_up;
+    const float nct = ct * ca - st * sa_dn;
+    st = nst; ct = nct;
+  }
+  // 2^e sin(t alpha - beta): the sine of l = +t
+  SQ_DEV float sin_plus(int t, float st, float ct) const {
+    return (t == 1 && s1 != 0.f) ? s1 : st * cb - ct * sb;
+  }
+  // 2^e sin(t alpha + beta): the sine of l = -t, sign dropped
+  SQ_DEV float sin_minus(float st, float ct) const { return st * cb + ct * sb; }
   // offset of a draw conditioned on |l| > kFejerWalk (rejection, telescoping proposal)
   SQ_DEV long long tail_ell(WordStream& ws) const {
     const double PI = 3.14159265358979323846;
@@ -122,21 +164,15 @@ struct FejerLaw {
     }
     // ---- walk
     float u = (float)ws.u();
-    // l = 0 : sin(-beta)
-    float den = sb * sb;
-    float acc = s * inv_m2 / den;
+    float acc = walk_term(sb);   // l = 0 : sin(-beta)
     long long ell = 0;
     bool found = acc >= u;
-    float st = 0.f, ct = 1.f;  // sin/cos(t*alpha)
+    float st = 0.f, ct = 1.f;  // 2^e sin / cos(t*alpha)
     for (int t = 1; t <= kFejerWalk && !found; ++t) {
-      float nst = st * ca + ct * sa;
-      float nct = ct * ca - st * sa;
-      st = nst; ct = nct;
-      float sp = st * cb - ct * sb;  // sin(t*alpha - beta)   (l = +t)
-      acc += s * inv_m2 / (sp * sp);
+      walk_step(st, ct);
+      acc += walk_term(sin_plus(t, st, ct));
       if (acc >= u) { ell = t; found = true; break; }
-      float sm = st * cb + ct * sb;  // -sin(-t*alpha - beta) (l = -t)
-      acc += s * inv_m2 / (sm * sm);
+      acc += walk_term(sin_minus(st, ct));
       if (acc >= u) { ell = -t; found = true; break; }
     }
     if (!found) ell = tail_ell(ws);
@@ -164,7 +200,8 @@ SQ_DEV long long ae_bins(double eps) {
   return (long long)ceil((PI / (2.0 * eps)) * (1.0 + sqrt(1.0 + 4.0 * eps)));
 }
 
-// small odd-length median (Q <= 31) by insertion sort in registers
+// small median (Q <= 31) by insertion sort in registers; an even Q averages
+// the two middle values, as the reference's np.median (Utility.py:571)
 template <int QMAX>
 SQ_DEV double median_of(double* v, int Q) {
   for (int i = 1; i < Q; ++i) {

@@ -178,17 +178,14 @@ SQ_DEV double ae_median_draws(double omega, long long M, int Q, WordStream& ws) 
     }
     float st = 0.f, ct = 1.f;
     for (int t = 1; t <= kFejerWalk && got < Q; ++t) {
-      const float nst = st * law.ca + ct * law.sa;
-      const float nct = ct * law.ca - st * law.sa;
-      st = nst;
-      ct = nct;
-      acc += law.walk_term(st * law.cb - ct * law.sb);   // l = +t
+      law.walk_step(st, ct);
+      acc += law.walk_term(law.sin_plus(t, st, ct));   // l = +t
       while (got < Q && un <= acc) {
         insert_sorted(c, circ(law.bin_of(t)));
         ++got;
         if (got < Q) un = next_u();
       }
-      acc += law.walk_term(st * law.cb + ct * law.sb);   // l = -t
+      acc += law.walk_term(law.sin_minus(st, ct));   // l = -t
       while (got < Q && un <= acc) {
         insert_sorted(c, circ(law.bin_of(-t)));
         ++got;

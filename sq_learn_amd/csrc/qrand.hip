@@ -35,7 +35,20 @@ __global__ void __launch_bounds__(256) philox_normal_kernel(
     float u1 = u01(blk.x), u2 = u01(blk.y);
     float r = sqrtf(-2.0f * logf(u1));
     float s, c; sincosf(6.28318530717958647f * u2, &s, &c);
-    float z = (e & 1) ? r * s : r * c;
+    float t = (e & 1) ? s : c;
+    // The rounded angle (and the rounded 2 pi) carry up to 1.2 * 2^-21 absolute
+    // into t.  That is below half a bf16 ulp of t (2^-9 |t|) down to
+    // |t| = 1.2 * 2^-12; next to a zero of t it is many.  Below 2^-11 take the
+    // quarter turns off u2 first (exact: u2 and q/4 are within a factor of two)
+    // and use the sine of the small remaining angle.  At q = 0 this is s itself.
+    if (fabsf(t) < 0x1p-11f) {
+      float q = rintf(4.0f * u2);
+      float p = sinf(6.28318530717958647f * (u2 - 0.25f * q));
+      // cos: -p at q = 1, +p at q = 3; sin: +p at q = 0 and 4, -p at q = 2
+      bool neg = (((int)q >> 1) ^ (int)(~e & 1)) & 1;
+      t = neg ? -p : p;
+    }
+    float z = r * t;
     float v = mean + stdv * z;
     if constexpr (sizeof(T) == 2) {
       reinterpret_cast<uint16_t*>(out)[i] = f32_to_bf16_rne(v);

@@ -26,6 +26,10 @@ SQ_API int sq_philox_uniform(void* out, long long n, unsigned k0, unsigned k1, u
 SQ_API int sq_ae_batch(const void* a, const void* eps, void* out, long long n, int Q, unsigned k0,
                        unsigned k1, unsigned s0, unsigned s1, unsigned long long offset,
                        void* stream);
+// out[i] = k / 2^m[i].  0 <= m[i] <= 40: the fp32 walk of fejer.h is scaled to
+// stay clear of underflow through M = 2^40 at every phase; the launcher does
+// not read m (device memory), ops/random.py phase_estimation_batch rejects
+// values outside the range.
 SQ_API int sq_pe_batch(const void* omega, const void* m, void* out, long long n, unsigned k0,
                        unsigned k1, unsigned s0, unsigned s1, unsigned long long offset,
                        void* stream);

@@ -12,6 +12,9 @@ from ..quantum.fejer import WALK, SMALL_M
 from . import _native as nat
 
 
+PE_MAX_QUBITS = 40   # largest m of phase_estimation_batch (M = 2^m bins)
+
+
 def _key_args(key: RngKey):
     return key.k0, key.k1, key.s0, key.s1
 
@@ -91,7 +94,8 @@ def fejer_sample_torch(omega, M, key: RngKey, sample_ids):
     out = torch.empty_like(base)
     w = torch.zeros_like(s_ids)
     u0 = _u_ws(key, s_ids, w)
-    sval = torch.sin(math.pi * phi) ** 2
+    # 1 - phi is exact above 1/2, pi * phi next to pi is not (csrc/fejer.h)
+    sval = torch.sin(math.pi * torch.where(phi > 0.5, 1.0 - phi, phi)) ** 2
 
     exact = phi == 0
     small = (~exact) & (M <= SMALL_M)
@@ -190,14 +194,25 @@ def amplitude_estimation_batch(a, eps, key: RngKey, Q=1, offset=0):
         j = fejer_sample_torch(omega, M, key, base + q)
         reps.append(torch.sin(math.pi * j.to(torch.float64) / M.to(torch.float64)) ** 2)
     st = torch.stack(reps, 0)
-    res = st[0] if Q == 1 else torch.sort(st, 0).values[Q // 2] if Q % 2 == 1 else torch.median(st, 0).values
+    # an even Q averages the two middle estimates, as the reference's
+    # np.median does (Utility.py:571) and csrc/fejer.h::median_of
+    srt = torch.sort(st, 0).values
+    res = srt[Q // 2] if Q % 2 == 1 else 0.5 * (srt[Q // 2 - 1] + srt[Q // 2])
     return res.reshape(a.shape)
 
 
 def phase_estimation_batch(omega, m, key: RngKey, offset=0):
-    """k/M samples, M = 2^m (per element), centred at omega in [0,1)."""
+    """k/M samples, M = 2^m (per element), centred at omega in [0,1).
+
+    ``0 <= m <= PE_MAX_QUBITS``: the range the fp32 walk of ``csrc/fejer.h``
+    is scaled for (see ``sq_api.h``); anything else raises."""
     omega = omega.to(torch.float64).contiguous()
     m = torch.broadcast_to(m.to(torch.int32), omega.shape).contiguous()
+    if m.numel():
+        lo, hi = (int(v) for v in torch.aminmax(m))
+        if lo < 0 or hi > PE_MAX_QUBITS:
+            raise ValueError(f"phase estimation supports 0 <= m <= {PE_MAX_QUBITS} qubits, "
+                             f"got m in [{lo}, {hi}]")
     if nat.use_native(omega):
         out = torch.empty_like(omega)
         nat.native().pe_batch(omega.data_ptr(), m.data_ptr(), out.data_ptr(), omega.numel(),

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import _qrand_ref as REF
 from sq_learn_amd.runtime.rng import RngKey, Philox
 from sq_learn_amd.ops import random as R
 from sq_learn_amd.ops import _native as nat
@@ -48,7 +49,10 @@ def test_ae_batch_distribution(cuda):
     a = torch.full((20000,), 0.3, dtype=torch.float64, device=cuda)
     eps = torch.full_like(a, 0.01)
     g = R.amplitude_estimation_batch(a, eps, key, Q=1).cpu().numpy()
-    c = R.amplitude_estimation_batch(a.cpu()[:2000], eps.cpu()[:2000], key, Q=1).numpy()
-    # same streams -> CPU twin reproduces the first 2000 device draws (rare fp32/fp64 boundary diffs)
-    assert np.mean(np.isclose(g[:2000], c)) > 0.99
+    # draw by draw the bins of the fp64 reference law (only draws within the
+    # fp32 walk's margin of a CDF boundary may take the neighbouring bin)
+    ev = REF.evaluate_case(dict(name="ae", op="ae", key=key.as_tuple(), offset=0, Q=1,
+                                x=a.cpu().numpy(), eps=eps.cpu().numpy()))
+    bad, excused, _ = REF.compare(g, ev)
+    assert bad.size == 0 and excused < 0.002
     assert abs(np.median(g) - 0.3) < 0.01

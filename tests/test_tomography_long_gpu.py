@@ -13,6 +13,7 @@ import pytest
 import torch
 from scipy import stats
 
+import _qrand_ref as REF
 from sq_learn_amd.quantum import device as QD
 from sq_learn_amd.quantum import reference as Q
 from sq_learn_amd.quantum.fejer import fejer_pmf
@@ -92,10 +93,12 @@ def test_pe_batch_kernel_law(cuda):
     g = R.phase_estimation_batch(torch.full((n,), omega, dtype=torch.float64, device=cuda),
                                  torch.full((n,), m, dtype=torch.int32, device=cuda),
                                  RngKey(4, "pe", 0)).cpu().numpy()
-    c = R.phase_estimation_batch(torch.full((2000,), omega, dtype=torch.float64),
-                                 torch.full((2000,), m, dtype=torch.int32),
-                                 RngKey(4, "pe", 0)).numpy()
-    assert np.mean(np.isclose(g[:2000], c)) > 0.99    # same Philox streams as the CPU twin
+    # draw by draw the bins of the fp64 reference law (only draws within the
+    # fp32 walk's margin of a CDF boundary may take the neighbouring bin)
+    ev = REF.evaluate_case(dict(name="pe", op="pe", key=RngKey(4, "pe", 0).as_tuple(), offset=0, Q=1,
+                                x=np.full(n, omega), m=np.full(n, m, dtype=np.int32)))
+    bad, excused, _ = REF.compare(g, ev)
+    assert bad.size == 0 and excused < 0.002
     M = 2 ** m
     k = np.round(g * M).astype(int)
     p = fejer_pmf(M * omega, M)
