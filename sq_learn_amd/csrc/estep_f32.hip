@@ -1773,15 +1773,43 @@ __global__ void __launch_bounds__(256) recheck_fast_kernel(
 // resolved - label, Hamerly upper bound and a new record - without reading its
 // fp32 row or any centroid row.  The rest are appended to the multi list for
 // the fp32 screen (which re-records them exactly).
-// Layout: a wave takes TWO rows per step (32 lanes each).  The vector
-// memory path is the screen's bound, so every load carries distinct data: the
-// per-row values (the 8-word record, |x|^2, the candidates' 8-word
-// per-centroid terms) come as ONE dword per lane (lane w of a row loads word
-// w) and are broadcast with lane shuffles, the list entries of 32 steps come
-// in one load; the records are read from the previous iteration's buffer and
-// written to the other one.  Three-stage pipeline: a step issues the next
-// step's record / |x|^2 words, computes, then issues the next step's fp16 row,
-// shift rows and per-centroid words (its record has landed meanwhile).
+// Layout: a wave takes blocks of 64 list rows; lane r owns row r of the block
+// (its record, |x|^2, its candidates' terms, the decision).  The dots x.S of
+// the block come from 32 passes of TWO rows (32 lanes each): pass p takes row
+// p on lanes 0..31 and row 32 + p on lanes 32..63, so everything a pass needs
+// from the owning lanes is ONE broadcast per value (lane p to the low half,
+// lane 32 + p to the high half: ds_bpermute).  The owning lane prepares those
+// values once per block: its row index and, per candidate, the 32-bit byte
+// offset of the shift row in dsh (slot and centroid folded in; the launcher
+// refuses a dsh of 4 GiB or more), which the loads add to the scalar base.
+// The candidate loads past the pass's wider row are skipped (two ballots per
+// block, c_r > 2 and c_r > 3, and a scalar bit test per pass).
+// A pass leaves, per candidate slot, one partial sum in each of the 32 lanes of
+// a row; four DPP adds reduce it within the rows of 16 lanes, two readlane
+// pairs finish the two rows and lanes p and 32 + p keep their row's sum.
+// (Measured at the headline shape, profiles/gap_screen_issue_structure.md: a
+// transposing butterfly over the passes - no readlane, no compare, a quarter
+// fewer vector instructions per pass - took the kernel from 273.9 to 277.1 us,
+// and no reduction at all gives 267: the reduction is not what bounds the
+// kernel, so the butterfly went back out.)
+// Rounding: an element's product enters a chain of DX / 64 fdot2 per lane and
+// then 5 adds, so gam = (DX + 16) 2^-24 stands.
+// What the compiler needs to keep NB passes in flight (each of these was a
+// full vmcnt(0) wait or a copy of the ring's 80 registers per four passes):
+// the last group of passes is peeled, so the loop's groups issue
+// unconditionally and the ring's registers are fixed; a scheduling barrier in
+// front of every pass keeps its loads behind the dots of the pass whose ring
+// slot they overwrite; the dots are pinned where they stand (the compiler
+// sinks them to their use, one pass later).  Per block, not per pass: the
+// record and list words at the start, |x|^2 and the candidates' dq terms under
+// the last four passes (only the decision needs them: 13 registers less
+// across the loop, 156 in all at d_pad = 256, three waves per SIMD).
+#ifndef SQ_GAP_ISSUE    // variant libraries only: 0 = readlane pairs + selects per value
+#define SQ_GAP_ISSUE 1
+#endif
+#ifndef SQ_GAP_REDUCE   // variant libraries only: 0 = no reduction (TIMING ONLY: the
+#define SQ_GAP_REDUCE 1   // sums are wrong on purpose)
+#endif
 typedef _Float16 gs_h2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float gs_dot(const uint4 a, const uint4 b, float acc) {
   acc = __builtin_amdgcn_fdot2(__builtin_bit_cast(gs_h2, a.x), __builtin_bit_cast(gs_h2, b.x), acc,
@@ -1808,16 +1836,18 @@ __device__ __forceinline__ float gs_dpp_add(float v) {
                                                          false));
 }
 __device__ __forceinline__ uint2 gs_zero(uint2) { return make_uint2(0u, 0u); }
-
+// (d_pad <= 256: three waves per SIMD - without the bound the register
+// allocator takes 209 registers at d_pad = 256 and a wave less)
 template <int DX>
-__global__ void __launch_bounds__(256) gap_screen_kernel(
+__global__ void __launch_bounds__(256, DX <= 256 ? 3 : 1) gap_screen_kernel(
     const _Float16* __restrict__ Xh, const float* __restrict__ xn,
     const long long* __restrict__ mrows_b, const int* __restrict__ count_b,
     const _Float16* __restrict__ dsh, long long dsh_stride, const float* __restrict__ dq,
     long long dq_stride, float inv_alpha, float delta, int* __restrict__ labels,
     GapRec* __restrict__ rec, int* __restrict__ mflag, int it_now, int ring, int rebase_age,
     long long* __restrict__ mrows, int* __restrict__ multi_count, long long cap,
-    int* __restrict__ n_done, long long* __restrict__ mrows_mv, int* __restrict__ count_mv) {
+    int* __restrict__ n_done, long long* __restrict__ mrows_mv, int* __restrict__ count_mv,
+    float* __restrict__ ydbg) {
   constexpr int LPR = 32;
   using VT = typename std::conditional<DX % 256 == 0, uint4, uint2>::type;
   constexpr int HV = (int)sizeof(VT) / 2;   // halves per vector
@@ -1825,7 +1855,6 @@ __global__ void __launch_bounds__(256) gap_screen_kernel(
   static_assert(DX % 128 == 0 && V >= 1, "gap screen: d_pad multiple of 128");
   const int lane = threadIdx.x & 63;
   const int sub = lane & (LPR - 1);
-  const bool hi = lane >= LPR;
   const long long cnt = min((long long)*count_b, cap);
   const long long gw = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   const long long nw = (long long)gridDim.x * (blockDim.x >> 6);
@@ -1860,12 +1889,15 @@ __global__ void __launch_bounds__(256) gap_screen_kernel(
     if (pred) buf[cnt + __popcll(pm & ((1ull << lane) - 1ull))] = row;
     cnt += __popcll(pm);
   };
+#if !SQ_GAP_ISSUE || SQ_GAP_REDUCE
   auto rl = [](int v, int l) -> int { return __builtin_amdgcn_readlane(v, l); };
   auto rlf = [](float v, int l) -> float {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
   };
+#endif
   for (long long blk = gw; blk < nblk; blk += nw) {
-    // ---- the lane's own row: entry, record, |x|^2, its candidates' terms
+    // ---- the lane's own row: entry, record (|x|^2 and its candidates' terms
+    // are fetched under the block's last passes: 13 registers less in the loop)
     const long long e = blk * 64 + lane;
     const bool live = e < cnt;
     const long long g = mrows_b[live ? e : cnt - 1];
@@ -1873,7 +1905,6 @@ __global__ void __launch_bounds__(256) gap_screen_kernel(
     const int rslot = base_it % ring, age = it_now - base_it;
     const float4* rp = reinterpret_cast<const float4*>(rec + g);
     const float4 r0 = rp[0], r1 = rp[1];
-    const float xq = xn[g];
     const unsigned id0 = __float_as_uint(r1.z), id1 = __float_as_uint(r1.w);
     const int c_r = (int)(id0 >> 30) + 1, slot = (int)((id0 >> 14) & 3u);
     int jc[kGapCand];
@@ -1881,23 +1912,56 @@ __global__ void __launch_bounds__(256) gap_screen_kernel(
     jc[1] = (int)((id0 >> 16) & 0x3FFFu);
     jc[2] = (int)(id1 & 0x3FFFu);
     jc[3] = (int)((id1 >> 16) & 0x3FFFu);
-    const float* dqs = dq + (size_t)rslot * dq_stride;
-    float4 d0[kGapCand];
-    float inv[kGapCand];
-#pragma unroll
-    for (int c = 0; c < kGapCand; ++c) {
-      d0[c] = reinterpret_cast<const float4*>(dqs)[2 * jc[c]];
-      inv[c] = dqs[8 * jc[c] + 4];
-    }
-    // ---- x.S for every row of the block: 32 passes of two rows (32 lanes
-    // per row), the fp16 row and its candidates' shift rows double-buffered;
-    // each pass's sums land in the owning lanes (v_writelane)
+    // ---- x.S for every row of the block: 32 passes of two rows (rows p and
+    // 32 + p, 32 lanes each), the fp16 row and its candidates' shift rows in a
+    // ring of NB passes in flight
     float y[kGapCand] = {0.0f, 0.0f, 0.0f, 0.0f};
     constexpr int NB = 4;   // passes in flight
     VT xv[NB][V], sv[NB][kGapCand][V];
+#if SQ_GAP_ISSUE
+    // what a pass needs from the owning lane, prepared once: the row index
+    // (64 bits: 10M x 256 fp16 is 5 GB) and the candidates' byte offsets in dsh
+    // (< 2^32: checked by the launcher)
+    const int xlo = (int)(unsigned)g, xhi = (int)(unsigned)((unsigned long long)g >> 32);
+    int coff[kGapCand];
+#pragma unroll
+    for (int c = 0; c < kGapCand; ++c)
+      coff[c] = (int)(unsigned)(((size_t)rslot * dsh_stride + (size_t)jc[c] * DX) * 2);
+    // bit p: pass p has a row with more than 2 (3) candidates
+    const unsigned long long b2 = __ballot(c_r > 2), b3 = __ballot(c_r > 3);
+    const unsigned wide2 = (unsigned)(b2 | (b2 >> 32)), wide3 = (unsigned)(b3 | (b3 >> 32));
+    auto wide = [&](int c, int p, int) -> bool {   // wave-uniform
+      return c < 2 || (((c == 2 ? wide2 : wide3) >> p) & 1u) != 0;
+    };
+    auto issue = [&](int p, int b) __attribute__((always_inline)) {
+      const int src = ((lane & LPR) + p) << 2;   // lane p of the lane's half
+      auto bc = [&](int v) -> unsigned { return (unsigned)__builtin_amdgcn_ds_bpermute(src, v); };
+      const char* xr = reinterpret_cast<const char*>(Xh) +
+                       ((((unsigned long long)bc(xhi) << 32) | bc(xlo)) * (DX * 2) +
+                        sub * sizeof(VT));
+#pragma unroll
+      for (int q = 0; q < V; ++q)
+        xv[b][q] = *reinterpret_cast<const VT*>(xr + q * LPR * (int)sizeof(VT));
+#pragma unroll
+      for (int c = 0; c < kGapCand; ++c) {
+        if (wide(c, p, b)) {
+          const unsigned o = bc(coff[c]) + (unsigned)(sub * (int)sizeof(VT));
+          const char* sr = reinterpret_cast<const char*>(dsh) + o;
+#pragma unroll
+          for (int q = 0; q < V; ++q)
+            sv[b][c][q] = *reinterpret_cast<const VT*>(sr + q * LPR * (int)sizeof(VT));
+        } else {
+#pragma unroll
+          for (int q = 0; q < V; ++q) sv[b][c][q] = gs_zero(VT{});
+        }
+      }
+    };
+#else
     int pcm[NB];   // the pass's widest row (candidate loads past it skipped)
-    auto issue = [&](int p, int b) {
-      const int ra = 2 * p, rb = 2 * p + 1;
+    auto wide = [&](int c, int, int b) -> bool { return c < 2 || c < pcm[b]; };
+    auto issue = [&](int p, int b) __attribute__((always_inline)) {
+      const int ra = p, rb = 32 + p;
+      const bool hi = lane >= LPR;
       const long long ga = ((long long)rl((int)(g >> 32), ra) << 32) | (unsigned)rl((int)g, ra);
       const long long gb = ((long long)rl((int)(g >> 32), rb) << 32) | (unsigned)rl((int)g, rb);
       const long long gm = hi ? gb : ga;
@@ -1909,7 +1973,7 @@ __global__ void __launch_bounds__(256) gap_screen_kernel(
       pcm[b] = max(rl(c_r, ra), rl(c_r, rb));
 #pragma unroll
       for (int c = 0; c < kGapCand; ++c) {
-        if (c < 2 || c < pcm[b]) {   // wave-uniform
+        if (wide(c, p, b)) {   // wave-uniform
           const int j = hi ? rl(jc[c], rb) : rl(jc[c], ra);
           const VT* sr = reinterpret_cast<const VT*>(ds + (size_t)j * DX);
 #pragma unroll
@@ -1920,32 +1984,73 @@ __global__ void __launch_bounds__(256) gap_screen_kernel(
         }
       }
     };
-    auto consume = [&](int p, int b) {
+#endif
+    // the pass's partial sums: one per lane and candidate slot (exactly 0 for
+    // a slot neither row of the pass has: its operand registers are zero)
+    auto dots = [&](int b, float (&acc)[kGapCand]) __attribute__((always_inline)) {
 #pragma unroll
       for (int c = 0; c < kGapCand; ++c) {
-        if (c < 2 || c < pcm[b]) {
-          float acc = 0.0f;
+        acc[c] = 0.0f;
 #pragma unroll
-          for (int q = 0; q < V; ++q) acc = gs_dot(xv[b][q], sv[b][c][q], acc);
-          acc = gs_dpp_add<0xB1>(acc);    // quad_perm [1,0,3,2]
-          acc = gs_dpp_add<0x4E>(acc);    // quad_perm [2,3,0,1]
-          acc = gs_dpp_add<0x141>(acc);   // row_half_mirror
-          acc = gs_dpp_add<0x140>(acc);   // row_mirror
-          const float a = rlf(acc, 0) + rlf(acc, 16), bb = rlf(acc, 32) + rlf(acc, 48);
-          y[c] = lane == 2 * p ? a : (lane == 2 * p + 1 ? bb : y[c]);
-        }
+        for (int q = 0; q < V; ++q) acc[c] = gs_dot(xv[b][q], sv[b][c][q], acc[c]);
       }
     };
 #pragma unroll
     for (int b = 0; b < NB - 1; ++b) issue(b, b);
-#pragma unroll 1
-    for (int p = 0; p < 32; p += NB) {
+    // a group of NB passes; the last group (TAIL) issues only pass 31, so the
+    // loop's groups issue unconditionally and the ring's registers are fixed
+    auto group = [&](const int p, auto TAIL_) __attribute__((always_inline)) {
+      constexpr bool TAIL = decltype(TAIL_)::value;
 #pragma unroll
       for (int b = 0; b < NB; ++b) {
-        if (p + b + NB - 1 < 32) issue(p + b + NB - 1, (b + NB - 1) % NB);
-        consume(p + b, b);
+        // the loads below overwrite the ring slot the previous pass read: kept
+        // behind its dots, or the slot gets a second set of registers and a
+        // copy (with a full vmcnt wait) per loop iteration
+        __builtin_amdgcn_sched_barrier(0);
+        if (!TAIL || b == 0) issue(p + b + NB - 1, (b + NB - 1) % NB);
+        float acc[kGapCand];
+        dots(b, acc);
+        // the sums are pinned here: left alone, the compiler may sink the dots
+        // toward their use, past the loads that reuse the pass's ring slot
+#pragma unroll
+        for (int c = 0; c < kGapCand; ++c) asm volatile("" : "+v"(acc[c]));
+#if SQ_GAP_REDUCE
+#pragma unroll
+        for (int c = 0; c < kGapCand; ++c) {
+          if (wide(c, p + b, b)) {
+            float a = acc[c];
+            a = gs_dpp_add<0xB1>(a);    // quad_perm [1,0,3,2]
+            a = gs_dpp_add<0x4E>(a);    // quad_perm [2,3,0,1]
+            a = gs_dpp_add<0x141>(a);   // row_half_mirror
+            a = gs_dpp_add<0x140>(a);   // row_mirror
+            const float lo = rlf(a, 0) + rlf(a, 16), up = rlf(a, 32) + rlf(a, 48);
+            y[c] = lane == p + b ? lo : (lane == 32 + p + b ? up : y[c]);
+          }
+        }
+#else
+#pragma unroll
+        for (int c = 0; c < kGapCand; ++c) y[c] += acc[c];
+#endif
       }
+    };
+#pragma unroll 1
+    for (int p = 0; p < 32 - NB; p += NB) group(p, std::false_type{});
+    // the lane's own |x|^2 and candidate terms, issued ahead of the last group
+    // (the ids are re-read from the record words: the loop keeps no copy)
+    unsigned il0 = id0, il1 = id1;
+    asm volatile("" : "+v"(il0), "+v"(il1));
+    const int jl[kGapCand] = {(int)(il0 & 0x3FFFu), (int)((il0 >> 16) & 0x3FFFu),
+                              (int)(il1 & 0x3FFFu), (int)((il1 >> 16) & 0x3FFFu)};
+    const float xq = xn[g];
+    const float* dqs = dq + (size_t)rslot * dq_stride;
+    float4 d0[kGapCand];
+    float inv[kGapCand];
+#pragma unroll
+    for (int c = 0; c < kGapCand; ++c) {
+      d0[c] = reinterpret_cast<const float4*>(dqs)[2 * jl[c]];
+      inv[c] = dqs[8 * jl[c] + 4];
     }
+    group(32 - NB, std::true_type{});
     // ---- the lane's own row: move the record, decide
     const float nx = sqrtf(xq) * (1.0f + 0x1p-16f);
     const float ex = 0x1p-11f * nx + sub_err, nxh = nx + ex;
@@ -1956,6 +2061,11 @@ __global__ void __launch_bounds__(256) gap_screen_kernel(
       yr[c] = y[c] * inv[c];
       E[c] = ex * d0[c].z + nxh * (d0[c].w + gam * (d0[c].z + d0[c].w)) + d0[c].y;
       qv[c] = d0[c].x;
+    }
+    if (ydbg && live) {   // kernel-uniform (tests: null in production)
+#pragma unroll
+      for (int c = 0; c < kGapCand; ++c)
+        if (c < c_r) ydbg[e * kGapCand + c] = yr[c];
     }
     float ya = 0.0f, Ea = 0.0f, qa = 0.0f;
 #pragma unroll
@@ -2021,8 +2131,8 @@ __global__ void __launch_bounds__(256) gap_screen_kernel(
       wp[1] = make_float4(gr[2], gr[3],
                           __uint_as_float((id0 & ~(3u << 14)) | (unsigned)m << 14),
                           __uint_as_float(id1));
-      if (m != slot) labels[g] = jc[0] * (m == 0) + jc[1] * (m == 1) + jc[2] * (m == 2) +
-                                 jc[3] * (m == 3);
+      if (m != slot) labels[g] = jl[0] * (m == 0) + jl[1] * (m == 1) + jl[2] * (m == 2) +
+                                 jl[3] * (m == 3);
       mflag[g] = it_now + 2;
     }
     // the rest -> the multi list (fp32 screen)
@@ -2308,6 +2418,39 @@ static int launch_estep_f32(const void* X, const void* C, const void* xn, void* 
   return sq_sum_partials(part, (int)grid * NW, inertia, st);
 }
 
+// The gap screen's one launch site (sq_estep_x64 and sq_gap_screen): one
+// resident round of long-lived waves (each takes blocks of 64 list rows), at
+// most `rblocks` blocks; grid_blocks > 0 overrides the grid, ydbg (float
+// [cap][4], tests) receives the scaled x.S of every listed row.
+template <int DX>
+static int launch_gap_screen(const void* Xh, const void* xn, const MultiRec& mrec, float inv_alpha,
+                             float delta, void* labels, void* mrows, void* multi_count,
+                             long long cap, long long rblocks, int grid_blocks, void* ydbg,
+                             hipStream_t st) {
+  // the kernel addresses dsh with 32-bit byte offsets
+  if (mrec.dsh_stride <= 0 || mrec.dsh_stride % DX != 0 ||
+      (unsigned long long)mrec.ring * (unsigned long long)mrec.dsh_stride * 2ull >= (1ull << 32))
+    return (int)hipErrorInvalidValue;
+  static long long gres = 0;
+  if (gres == 0) {
+    int dev = 0, cus = 0, per_cu = 0;
+    hipGetDevice(&dev);
+    hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)gap_screen_kernel<DX>, 256,
+                                                 0);
+    gres = (long long)(cus > 0 ? cus : 256) * (per_cu > 0 ? per_cu : 2);
+  }
+  const unsigned bgrid =
+      grid_blocks > 0 ? (unsigned)grid_blocks : (unsigned)min(max(rblocks, 1LL), gres);
+  hipLaunchKernelGGL(gap_screen_kernel<DX>, dim3(bgrid), dim3(256), 0, st, (const _Float16*)Xh,
+                     (const float*)xn, mrec.mrows_b, mrec.count_b, mrec.dsh, mrec.dsh_stride,
+                     mrec.dq, mrec.dsh_stride / DX * 8, inv_alpha, delta, (int*)labels, mrec.rec,
+                     mrec.mflag, mrec.it_now, mrec.ring, max(1, mrec.ring / 2), (long long*)mrows,
+                     (int*)multi_count, cap, mrec.n_done, mrec.mrows_mv, mrec.count_mv,
+                     (float*)ydbg);
+  return (int)hipGetLastError();
+}
+
 template <int KSD>
 static int launch_estep_x64(const void* Xh, const void* X, const void* C, const void* Cm,
                             const void* xn, const void* cmax2, void* labels, void* mind,
@@ -2367,24 +2510,9 @@ static int launch_estep_x64(const void* Xh, const void* X, const void* C, const 
   if (xflag && mrec.rec && ub) {
     if constexpr (KSD * 16 % 128 == 0) {
       // list B first: its uncertain rows join the multi list
-      // one resident round of long-lived waves (each takes blocks of 64 rows)
-      static long long gres = 0;
-      if (gres == 0) {
-        int dev = 0, cus = 0, per_cu = 0;
-        hipGetDevice(&dev);
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &per_cu, (const void*)gap_screen_kernel<KSD * 16>, 256, 0);
-        gres = (long long)(cus > 0 ? cus : 256) * (per_cu > 0 ? per_cu : 2);
-      }
-      const unsigned bgrid = (unsigned)min(max(rblocks, 1LL), gres);
-      hipLaunchKernelGGL(gap_screen_kernel<KSD * 16>, dim3(bgrid), dim3(256), 0, st,
-                         (const _Float16*)Xh, (const float*)xn, mrec.mrows_b, mrec.count_b,
-                         mrec.dsh, mrec.dsh_stride, mrec.dq,
-                         mrec.dsh_stride / (KSD * 16) * 8, 1.0f / alpha, (float)delta,
-                         (int*)labels, mrec.rec, mrec.mflag, mrec.it_now, mrec.ring,
-                         max(1, mrec.ring / 2), (long long*)mrows, (int*)multi_count, n,
-                         mrec.n_done, mrec.mrows_mv, mrec.count_mv);
+      rc = launch_gap_screen<KSD * 16>(Xh, xn, mrec, 1.0f / alpha, (float)delta, labels, mrows,
+                                       multi_count, n, rblocks, 0, nullptr, st);
+      if (rc) return rc;
     }
   }
   if (xflag) {
@@ -2560,6 +2688,40 @@ int sq_estep_x64(const void* Xh, const void* X, const void* C, const void* Cm, c
   }
   if (rc) return rc;
   return (int)hipGetLastError();
+}
+
+// The gap screen alone (tests, benchmarks/gap_screen_micro.py): the launch
+// sq_estep_x64 makes for list B, on the caller's buffers.  n: the capacity of
+// the lists (and the row count the default grid is sized from); grid_blocks
+// (0: default) overrides the grid; ydbg (null: off): float [n][4], the scaled
+// x.S of candidate slot c < c_r of the row at each list position.
+int sq_gap_screen(const void* Xh, const void* xn, const void* mrows_b, const void* count_b,
+                  const void* dsh, const void* dq, long long dsh_stride, int ring, double alpha,
+                  double delta, void* labels, void* rec, void* rec_mflag, int it_now, void* mrows,
+                  void* multi_count, void* n_done, void* mrows_mv, void* count_mv, long long n,
+                  int d_pad, int grid_blocks, void* ydbg, void* stream) {
+  if ((mrows_mv != nullptr) != (count_mv != nullptr)) return (int)hipErrorInvalidValue;
+  if (!Xh || !xn || !mrows_b || !count_b || !dsh || !dq || !labels || !rec || !rec_mflag ||
+      !mrows || !multi_count || it_now < 1 || ring < 2 || ring > 16 || grid_blocks < 0)
+    return (int)hipErrorInvalidValue;
+  int aexp = 0;
+  if (!(alpha > 0.0) || frexp(alpha, &aexp) != 0.5) return (int)hipErrorInvalidValue;
+  if (n <= 0) return 0;
+  const MultiRec mrec{(GapRec*)rec, (int*)rec_mflag, it_now, it_now, ring, (const _Float16*)dsh,
+                      (const float*)dq, dsh_stride, (long long*)mrows_b, (int*)count_b,
+                      (int*)n_done, (long long*)mrows_mv, (int*)count_mv};
+  const long long rblocks = (n / 16 + 63) / 64;   // as in launch_estep_x64
+  hipStream_t st = (hipStream_t)stream;
+  switch (d_pad) {
+#define CASE(DX)                                                                                 \
+  case DX:                                                                                       \
+    return launch_gap_screen<DX>(Xh, xn, mrec, (float)(1.0 / alpha), (float)delta, labels, mrows, \
+                                 multi_count, n, rblocks, grid_blocks, ydbg, st);
+    CASE(128) CASE(256) CASE(384) CASE(512) CASE(640) CASE(768) CASE(896) CASE(1024)
+#undef CASE
+    default:
+      return (int)hipErrorInvalidValue;
+  }
 }
 
 #if SQ_X64_STAMP

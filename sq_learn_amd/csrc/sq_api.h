@@ -312,6 +312,17 @@ SQ_API int sq_estep_x64(const void* Xh, const void* X, const void* C, const void
                         const void* dsh, const void* dq, long long dsh_stride, void* mrows_b,
                         void* count_b, void* n_done, void* mrows_mv, void* count_mv,
                         void* ovf2_rows, void* ovf2_count);
+// The gap screen of sq_estep_x64 alone, on the caller's buffers (n: capacity
+// of the lists).  grid_blocks (0: the default grid) and ydbg (null: off; float
+// [n][4], the scaled x.S per list position and candidate slot) are for tests
+// and timing (ops/kmeans.py calls it through ctypes: the module's method table
+// lists what the estimators call).
+SQ_API int sq_gap_screen(const void* Xh, const void* xn, const void* mrows_b, const void* count_b,
+                         const void* dsh, const void* dq, long long dsh_stride, int ring,
+                         double alpha, double delta, void* labels, void* rec, void* rec_mflag,
+                         int it_now, void* mrows, void* multi_count, void* n_done, void* mrows_mv,
+                         void* count_mv, long long n, int d_pad, int grid_blocks, void* ydbg,
+                         void* stream);
 // (diagnostic builds with -DSQ_X64_STAMP=1 only; host: a host buffer)
 SQ_API int sq_x64_stamps(void* host, int n_waves);
 SQ_API int sq_x64_stamps_clear();

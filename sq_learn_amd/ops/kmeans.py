@@ -507,6 +507,52 @@ def shift_operand_native(C_prev, C_new, alpha, snap, dsh, dq, snew, valid):
                                nat.stream_handle(C_new.device))
 
 
+_GAP_SCREEN = None
+
+
+def _gap_screen_entry():
+    """``sq_gap_screen`` of the loaded extension, through ctypes: a test and
+    timing entry, prototyped in csrc/sq_api.h like every launcher but (as
+    ``sq_x64_stamps``) not in the module's method table, which lists what the
+    estimators call."""
+    global _GAP_SCREEN
+    if _GAP_SCREEN is None:
+        import ctypes
+        P, L, I, D = ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_double
+        fn = ctypes.CDLL(nat.loaded_path()).sq_gap_screen
+        fn.restype = I
+        # the prototype of csrc/sq_api.h, in its order
+        fn.argtypes = [P, P, P, P, P, P, L, I, D, D, P, P, P, I, P, P, P, P, P, L, I, I, P, P]
+        _GAP_SCREEN = fn
+    return _GAP_SCREEN
+
+
+def gap_screen_native(Xh, xn, labels, multi_rows, multi_count, records: MultiRecords, alpha,
+                      delta, grid_blocks=0, ydbg=None):
+    """The certified E-step's gap screen alone (``sq_gap_screen``, csrc/
+    estep_f32.hip gap_screen_kernel) on list B of ``records``: resolved rows
+    keep or get their label and record, the rest are appended to
+    ``multi_rows`` / ``multi_count``.  ``grid_blocks`` (0: the launcher's
+    grid) and ``ydbg`` (float32 [n, 4]: the scaled x.S of candidate slot c <
+    c_r at each list position) are for tests and timing."""
+    n, d_pad = Xh.shape
+    assert Xh.dtype == torch.float16 and Xh.is_contiguous() and xn.dtype == torch.float32
+    assert labels.dtype == torch.int32 and multi_rows.dtype == torch.int64
+    assert multi_rows.numel() >= n and multi_count.dtype == torch.int32
+    if ydbg is not None:
+        assert ydbg.dtype == torch.float32 and ydbg.is_contiguous() and ydbg.numel() >= 4 * n
+    r = records
+    p = lambda a: a or None   # noqa: E731  (address 0 -> NULL)
+    rc = _gap_screen_entry()(
+        Xh.data_ptr(), xn.data_ptr(), r.rows_b, r.count_b, r.dsh, r.dq, r.dsh_stride, r.ring,
+        float(alpha), float(delta), labels.data_ptr(), r.rec, r.mflag, r.it_now,
+        multi_rows.data_ptr(), multi_count.data_ptr(), p(r.n_done), p(r.rows_moved),
+        p(r.count_moved), int(n), int(d_pad), int(grid_blocks), p(nat.ptr(ydbg)),
+        p(nat.stream_handle(Xh.device)))
+    if rc != 0:
+        raise RuntimeError(f"sq_learn_amd native launch failed: sq_gap_screen ({rc})")
+
+
 def ensure_multi_buffers(buf: EStepBuffers, n, device, bounds=False):
     """Allocate the certified E-step's row lists (and, with ``bounds``, the
     per-row multi flag of the Hamerly pruning)."""
