@@ -42,6 +42,10 @@ namespace sq {
 constexpr int kKppTile = 32;          // fp32 features per staged tile (128 B of a row)
 constexpr int kKppInitGrid = 16384;   // workgroups of the first-centre pass
 constexpr int kKppStride = 36;        // LDS row stride in floats (16-B aligned, skewed banks)
+// widest int8 row of the certified bound: its workgroup stages the two-term
+// candidates [2][16][dq] in LDS, 32 dq <= 64 KiB.  Wider rows run without the
+// screens (ops/kmeans.py KMPP_BOUND_MAX_DQ; same results, every row exact).
+constexpr int kKppBoundMaxDq = 2048;
 
 SQ_DEV double kpp_q(float v, double wi, double scale) { return rint((double)v * wi * scale); }
 
@@ -1488,7 +1492,7 @@ int sq_kmpp_bound(const void* Xq, int dq, const void* srow, const void* erow, co
                   long long n, long long R, int G, const void* surv, const void* scount,
                   void* exact, void* ecount, void* stream) {
   if (n <= 0) return 0;
-  if (t < 1 || t > 16 || (dq & 63) || dq < d || R <= 0 || G <= 0 || 32 * dq > 65536)
+  if (t < 1 || t > 16 || (dq & 63) || dq < d || R <= 0 || G <= 0 || dq > kKppBoundMaxDq)
     return (int)hipErrorInvalidValue;
 #define LAUNCH(NS)                                                                              \
   hipLaunchKernelGGL(kmpp_bound_kernel<NS>, dim3(G), dim3(256), (size_t)32 * dq,                \
@@ -1509,7 +1513,7 @@ int sq_kmpp_bound(const void* Xq, int dq, const void* srow, const void* erow, co
 
 int sq_kmpp_dots(const void* Xq, int dq, long long n, const void* candq, void* out, void* stream) {
   if (n <= 0) return 0;
-  if ((dq & 63) || 32 * dq > 65536) return (int)hipErrorInvalidValue;
+  if ((dq & 63) || dq > kKppBoundMaxDq) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(kmpp_dots_kernel, dim3((unsigned)((n + 15) / 16)), dim3(64), (size_t)32 * dq,
                      (hipStream_t)stream, (const int8_t*)Xq, dq, n, (const int8_t*)candq,
                      (int*)out);
@@ -1621,7 +1625,7 @@ int sq_kmpp_batch(int op, const long long* ia, void* stream) {
       hipLaunchKernelGGL(kmpp_screen_batch_kernel, dim3(rows_grid), dim3(256), 0, st, a);
       break;
     case 3: {
-      if (!a.Xq || (a.dq & 63) || a.dq < a.d || 32 * a.dq > 65536) return (int)hipErrorInvalidValue;
+      if (!a.Xq || (a.dq & 63) || a.dq < a.d || a.dq > kKppBoundMaxDq) return (int)hipErrorInvalidValue;
 #define LAUNCH(NS)                                                                              \
   hipLaunchKernelGGL(kmpp_bound_batch_kernel<NS>, dim3(rows_grid), dim3(256), (size_t)32 * a.dq, st, a)
       switch (a.dq / 64) {

@@ -934,6 +934,9 @@ def sum_f32_native(v, n, part, out, extra=0):
 
 
 # ------------------------------------------------- k-means++ (exact, pruned)
+KMPP_BOUND_MAX_DQ = 2048   # csrc/kmpp.hip kKppBoundMaxDq: wider rows run unscreened
+
+
 class KmppState:
     """Device state of the exact accelerated k-means++ (csrc/kmpp.hip) on
     one shard: per-row closest distance (fp32) and nearest chosen centre, the
@@ -953,8 +956,8 @@ class KmppState:
         self.X, self.n, self.d, self.t, self.k = Xf, n, d, t, int(k)
         self.ldx = Xf.stride(0)
         self.w = None if w is None else w.to(device=dev, dtype=torch.float64).contiguous()
-        self.prune = bool(prune) and d <= 8192
         self.dq = -(-d // 64) * 64
+        self.prune = bool(prune) and self.dq <= KMPP_BOUND_MAX_DQ
         self.dev = dev
         m = nat.native()
         self.m = m
@@ -1152,7 +1155,7 @@ class KmppBatch:
         # dq <= 256); SQ_KMPP_FUSED=0: the per-restart passes (same ids)
         st0 = self.states[0]
         self.tp = 1 << max(0, (self.t - 1).bit_length())
-        self.fused = (prune and self.n > 0 and nr <= 16 and nr * self.tp <= 128
+        self.fused = (st0.prune and self.n > 0 and nr <= 16 and nr * self.tp <= 128
                       and st0.dq <= 256 and os.environ.get("SQ_KMPP_FUSED", "1") != "0")
         # exact pass with a lane per (row, trial) (op 9; d <= 256);
         # SQ_KMPP_EXACT2=0: a lane per row (op 4, same results)

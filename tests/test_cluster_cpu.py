@@ -13,6 +13,8 @@ from sq_learn_amd.base import clone
 from sq_learn_amd.models.cluster import QMeans, KMeans, k_means, kmeans_plusplus
 from sq_learn_amd.utils.datasets import make_blobs
 
+from _kmpp_ref import kpp_oracle as _kpp_oracle
+
 warnings.simplefilter("ignore")
 
 
@@ -223,27 +225,6 @@ def test_elkan_single_cluster_warns():
     X = np.random.RandomState(0).randn(50, 3)
     with pytest.warns(RuntimeWarning, match="single cluster"):
         KMeans(1, algorithm="elkan", n_init=1).fit(X)
-
-
-def _kpp_oracle(X, k, rs, t=None):
-    """The reference's greedy k-means++ (``cluster/_kmeans.py:153-247``),
-    verbatim semantics in numpy fp64."""
-    n = X.shape[0]
-    t = t or 2 + int(np.log(k))
-    xn = (X * X).sum(1)
-    idx = [rs.randint(n)]
-    closest = np.maximum(xn + xn[idx[0]] - 2 * X @ X[idx[0]], 0)
-    pot = closest.sum()
-    for _ in range(1, k):
-        vals = rs.random_sample(t) * pot
-        cand = np.clip(np.searchsorted(np.cumsum(closest), vals), None, n - 1)
-        D = np.maximum(xn[None, :] + xn[cand][:, None] - 2 * X[cand] @ X.T, 0)
-        D = np.minimum(closest, D)
-        p = D.sum(1)
-        b = int(np.argmin(p))
-        pot, closest = p[b], D[b]
-        idx.append(cand[b])
-    return np.array(idx)
 
 
 @pytest.mark.parametrize("k", [3, 17])
