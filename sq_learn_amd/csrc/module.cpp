@@ -232,7 +232,14 @@ static PyMethodDef logistic_methods[] = {
     SQ_FN(sp_matvec, NOGIL, "CSR x fp64 vector product over row segments"),
     {nullptr, nullptr, 0, nullptr}};
 
-static struct PyModuleDef moddef = {PyModuleDef_HEAD_INIT, "_C",
+// spgram.hip: the submodule ``_C.gram``.  Its format table is
+// tests/golden/native_formats_gram.json.
+static PyMethodDef gram_methods[] = {
+    SQ_FN(sp_gram, 0, "CSR x CSR kernel matrix through an inverted index"),
+    SQ_FN(sp_gram_matvec, 0, "CSR x CSR kernel matrix applied to vectors, never formed"),
+    {nullptr, nullptr, 0, nullptr}};
+
+static struct PyModuleDef moddef ={PyModuleDef_HEAD_INIT, "_C",
                                     "sq_learn_amd native HIP kernels (gfx950)", -1, methods};
 static struct PyModuleDef lda_moddef = {PyModuleDef_HEAD_INIT, "sq_learn_amd._C.lda",
                                         "latent Dirichlet allocation kernels (splda.hip)", -1,
@@ -243,6 +250,9 @@ static struct PyModuleDef nmf_moddef = {PyModuleDef_HEAD_INIT, "sq_learn_amd._C.
 static struct PyModuleDef logistic_moddef = {PyModuleDef_HEAD_INIT, "sq_learn_amd._C.logistic",
                                              "logistic-regression loss kernels (splogit.hip)", -1,
                                              logistic_methods};
+static struct PyModuleDef gram_moddef = {PyModuleDef_HEAD_INIT, "sq_learn_amd._C.gram",
+                                         "sparse kernel-matrix kernels (spgram.hip)", -1,
+                                         gram_methods};
 
 static bool add_submodule(PyObject* m, const char* name, PyModuleDef* def) {
   PyObject* sub = PyModule_Create(def);
@@ -257,7 +267,8 @@ PyMODINIT_FUNC PyInit__C(void) {
   PyObject* m = PyModule_Create(&moddef);
   if (!m) return nullptr;
   if (!add_submodule(m, "lda", &lda_moddef) || !add_submodule(m, "nmf", &nmf_moddef) ||
-      !add_submodule(m, "logistic", &logistic_moddef)) {
+      !add_submodule(m, "logistic", &logistic_moddef) ||
+      !add_submodule(m, "gram", &gram_moddef)) {
     Py_DECREF(m);
     return nullptr;
   }

@@ -188,6 +188,20 @@ SQ_API int sq_sp_matvec(const void* indptr, const void* indices, const void* dat
                         long long nlong, const void* x, int cols, void* y, void* scratch,
                         void* stream);
 
+// spgram.hip (kind: 0 linear, 1 poly, 2 rbf, 3 sigmoid; out: the first row of the
+// whole result, row q at out + q * ld)
+SQ_API int sq_sp_gram(const void* qptr, const void* qidx, const void* qval, const void* trow,
+                      const void* tval, const void* tab, const void* qn, const void* xn,
+                      const void* qexp, long long q0, long long m, long long n, int d, int T,
+                      long long nnz_x, int kind, double gamma, double coef0, double degree,
+                      int self_join, double diag_add, void* out, long long ld, void* stream);
+SQ_API int sq_sp_gram_matvec(const void* qptr, const void* qidx, const void* qval,
+                             const void* trow, const void* tval, const void* tab, const void* qn,
+                             const void* xn, const void* qexp, long long q0, long long m,
+                             long long n, int d, int T, long long nnz_x, int kind, double gamma,
+                             double coef0, double degree, int self_join, const void* V, int R,
+                             void* part, void* out, void* stream);
+
 // failure.hip
 SQ_API int sq_failure_inject(void* labels, long long n, int k, double p, int R, unsigned k0,
                              unsigned k1, unsigned s0, unsigned s1, unsigned t0, unsigned t1,

@@ -16,11 +16,21 @@ from scipy's cg as an array and had the b / alpha formulas swapped - here
 b = 1^T eta / 1^T nu, alpha = eta - nu b with H eta = y, H nu = 1, which
 equals the direct solve; ``LSSVC.get_P`` used ||x_i|| in place of ||x_j||^2 -
 here it uses QLSSVC's beta = sqrt((N ||x||^2 + 1) Nu).
+
+Sparse input: scipy sparse ``X`` stays CSR (``self.X`` is the scipy matrix;
+the device copy and its caches are private runtime state, dropped on
+pickling).  The K block of F is written in place by
+``ops.sparse_kernel.sp_kernel_matrix`` (``csrc/spgram.hip``), decision values
+are ``sp_kernel_matvec(train, queries, alpha) + b`` without the M x N block,
+and LSSVC 'cg' runs matrix-free once the N x N matrix would exceed
+``SQ_SVM_DENSE_BYTES`` (there a kernel that is not positive semidefinite is
+refused: no ``lstsq`` fallback exists without the matrix).  On a GPU the stored values are fp32.
 """
 
 import math
 
 import numpy as np
+import scipy.sparse as sp
 import torch
 
 from ...base import BaseEstimator, ClassifierMixin
@@ -30,11 +40,48 @@ from ...utils.metrics import accuracy_score
 from ...runtime.device import resolve_device, to_numpy
 from ...runtime.rng import RngKey
 from ...ops.random import trunc_normal_add_
+from ...ops._csr import sp_row_norms
+from ...ops.sparse_knn import TILE_DEFAULT, InvertedIndex
+from ...ops.sparse_kernel import sp_kernel_matrix, sp_kernel_matvec
+from ...ops.sparse_linalg import sp_xty
+from .._data import SparseData, as_sparse_data
+from ._libsvm import _dense_limit_bytes
+
+
+# a smallest Ritz value this far (relative to the largest) below 1 / penalty is a
+# negative eigenvalue of K, not the rounding of the Lanczos recurrence
+_RITZ_TOL = 2.0 ** -26
+
+
+def _ritz_range(coeffs, tol):
+    """(smallest, largest) eigenvalue over the Lanczos tridiagonals that the CG
+    coefficients of ``conjugate_gradient`` define, one per right-hand side:
+    diagonal ``1 / alpha_k + beta_{k-1} / alpha_{k-1}``, off-diagonal
+    ``sqrt(beta_k) / alpha_k``.  A column counts up to the iteration at which
+    it met ``tol``: the steps it takes while another column still runs are
+    rounding."""
+    al, be, rel = (torch.stack([c[i] for c in coeffs]).cpu().numpy() for i in range(3))
+    lo, hi = np.inf, -np.inf
+    for c in range(al.shape[1]):
+        done = np.nonzero(rel[:, c] <= tol ** 2)[0]
+        k = int(done[0]) + 1 if done.size else al.shape[0]
+        a, b = al[:k, c], be[:k, c]
+        d = 1.0 / a
+        d[1:] += b[:-1] / a[:-1]
+        e = np.sqrt(b[:-1]) / a[:-1]
+        ev = np.linalg.eigvalsh(np.diag(d) + np.diag(e, 1) + np.diag(e, -1))
+        lo, hi = min(lo, ev[0]), max(hi, ev[-1])
+    return float(lo), float(hi)
 
 
 class _KernelMixin:
     def _get_gamma(self, X):
         if self.gamma == "scale":
+            if sp.issparse(X):
+                # the variance over all n * d entries from the stored values
+                size = X.shape[0] * X.shape[1]
+                mean = X.data.sum() / size
+                return 1.0 / (X.shape[1] * (np.square(X.data).sum() / size - mean * mean))
             Xn = to_numpy(X) if isinstance(X, torch.Tensor) else np.asarray(X)
             return 1.0 / (Xn.shape[1] * Xn.var())
         if self.gamma == "auto":
@@ -61,8 +108,91 @@ class _KernelMixin:
         dev = resolve_device(getattr(self, "device", None))
         return dev
 
+    # ------------------------------------------------------- sparse rows
+    def _fit_input(self, X, y):
+        """Validated (X, y): scipy sparse ``X`` of any format as canonical
+        fp64 CSR, anything else as a dense fp64 array."""
+        X, y = self._validate_data(X, y, accept_sparse=True)
+        self._engine_sparse = None
+        if sp.issparse(X):
+            X = X.tocsr().astype(np.float64)         # a copy: the caller's matrix stays as it is
+            if not X.has_canonical_format:
+                X.sum_duplicates()
+                X.sort_indices()
+        else:
+            X = np.asarray(to_numpy(X), dtype=np.float64)
+        return X, np.asarray(to_numpy(y), dtype=np.float64)
+
+    def _sparse_fit(self):
+        """True for an estimator fitted on scipy sparse rows."""
+        return sp.issparse(getattr(self, "X", None))
+
+    def _train(self):
+        """(SparseData, InvertedIndex of the self-join) of the training rows
+        on the estimator device: uploaded once, runtime state only."""
+        eng = getattr(self, "_engine_sparse", None)
+        if eng is None:
+            sd = as_sparse_data(self.X, self._device())
+            op = InvertedIndex(sd, sd, TILE_DEFAULT) if sd.device.type == "cuda" else None
+            eng = self._engine_sparse = (sd, op)
+        return eng
+
+    def _queries(self, X):
+        """Query rows of an estimator fitted on CSR as a ``SparseData`` on its
+        device; dense rows are converted to CSR."""
+        if isinstance(X, SparseData):
+            return X
+        if not sp.issparse(X):
+            X = sp.csr_matrix(np.asarray(to_numpy(check_array(X)), dtype=np.float64))
+        self._check_n_features(X, reset=False)
+        return as_sparse_data(X, self._device())
+
+    def _check_queries(self, X):
+        """``check_array`` of the predict methods: sparse queries only for an
+        estimator fitted on sparse rows."""
+        check_is_fitted(self, "alpha_")
+        if self._sparse_fit():
+            return self._queries(X)
+        return check_array(X)
+
+    def _kernel_params(self):
+        if self.kernel not in ("linear", "poly", "rbf", "sigmoid"):
+            raise ValueError(f"unknown kernel {self.kernel!r}")
+        gamma = 1.0 if self.kernel == "linear" else self._get_gamma(self._gamma_ref)
+        return dict(kind=self.kernel, gamma=gamma, coef0=self.coef0, degree=self.degree)
+
+    def _sparse_H(self, out=None):
+        """K + I / penalty of the training rows in one pass, into ``out``."""
+        sd, op = self._train()
+        return sp_kernel_matrix(sd, sd, out=out, diag_add=1.0 / self.penalty, op=op,
+                                **self._kernel_params())
+
+    def _row_sq(self, X):
+        """Squared row norms (numpy) of dense rows or a ``SparseData``."""
+        if isinstance(X, SparseData):
+            return sp_row_norms(X).cpu().numpy()
+        return np.sum(np.asarray(to_numpy(X), dtype=np.float64) ** 2, 1)
+
+    def _train_row_sq(self):
+        return self._row_sq(self._train()[0] if self._sparse_fit() else self.X)
+
+    def _xt(self, v):
+        """X^T v over the training rows (numpy)."""
+        if not self._sparse_fit():
+            return v @ self.X
+        sd = self._train()[0]
+        return sp_xty(sd, torch.as_tensor(np.asarray(v, dtype=np.float64))[:, None])[:, 0] \
+            .cpu().numpy()
+
     def _F(self, X):
         N = X.shape[0]
+        if sp.issparse(X):
+            F = torch.empty((N + 1, N + 1), dtype=torch.float64, device=self._train()[0].device)
+            F[0, 0] = 0.0
+            F[0, 1:] = 1.0
+            F[1:, 0] = 1.0
+            self._sparse_H(out=F[1:, 1:])
+            return F
         K = self.get_kernel(X)
         dev = K.device
         F = torch.zeros((N + 1, N + 1), dtype=torch.float64, device=dev)
@@ -73,12 +203,22 @@ class _KernelMixin:
 
     def get_h(self, X):
         check_is_fitted(self, "alpha_")
+        if self._sparse_fit():
+            # K(queries, train) alpha + b without the M x N block
+            h = sp_kernel_matvec(self._train()[0], self._queries(X),
+                                 torch.as_tensor(self.alpha_, dtype=torch.float64),
+                                 **self._kernel_params())
+            return (h + self.b_).cpu().numpy()
+        if sp.issparse(X) or isinstance(X, SparseData):
+            raise TypeError("A sparse matrix was passed, but dense data is required: the "
+                            "estimator was fitted on dense rows. Use X.toarray() to convert to "
+                            "a dense numpy array.")
         Kx = self.get_kernel(self.X, X)
         return (torch.as_tensor(self.alpha_, device=Kx.device).double() @ Kx.double()
                 + self.b_).cpu().numpy()
 
     def _gram_for_gamma(self, X):
-        self._gamma_ref = np.asarray(to_numpy(X), dtype=np.float64)
+        self._gamma_ref = X if sp.issparse(X) else np.asarray(to_numpy(X), dtype=np.float64)
 
 
 class LSSVC(_KernelMixin, ClassifierMixin, BaseEstimator):
@@ -110,8 +250,13 @@ class LSSVC(_KernelMixin, ClassifierMixin, BaseEstimator):
 
     def _cg_fit(self, X, y):
         N = X.shape[0]
-        H = self.get_kernel(X).double()
-        H = H + (1.0 / self.penalty) * torch.eye(N, dtype=torch.float64, device=H.device)
+        if sp.issparse(X):
+            if 8 * N * N > _dense_limit_bytes():
+                return self._cg_fit_matrix_free(y)
+            H = self._sparse_H()
+        else:
+            H = self.get_kernel(X).double()
+            H = H + (1.0 / self.penalty) * torch.eye(N, dtype=torch.float64, device=H.device)
         B = torch.stack([torch.as_tensor(y, dtype=torch.float64, device=H.device),
                          torch.ones(N, dtype=torch.float64, device=H.device)], 1)
         Z = conjugate_gradient(H, B, tol=self.cg_tol, maxiter=self.cg_maxiter)
@@ -119,15 +264,54 @@ class LSSVC(_KernelMixin, ClassifierMixin, BaseEstimator):
         if not bool(torch.isfinite(Z).all()) or float(res) > 1e-6:
             # H is not SPD (e.g. sigmoid kernel): CG does not apply, solve directly
             Z = torch.linalg.lstsq(H, B).solution
+        return self._cg_solution(Z)
+
+    def _cg_fit_matrix_free(self, y):
+        """CG on H = K + I / penalty of CSR rows whose N x N matrix exceeds
+        ``SQ_SVM_DENSE_BYTES``: H is applied to the two right-hand sides at a
+        time by the fused kernel and never formed.  Without the matrix there
+        is no ``lstsq`` fallback, so the run is accepted only when it ends
+        with the residual test passed and the kernel seen as positive
+        semidefinite: the CG coefficients are the Lanczos tridiagonal of H,
+        whose eigenvalues (Ritz values) lie inside the spectrum of H, so a
+        smallest Ritz value below ``1 / penalty`` (beyond rounding) certifies
+        a negative eigenvalue of K.  Anything else raises."""
+        sd, op = self._train()
+        params = self._kernel_params()
+        ridge = 1.0 / self.penalty
+
+        def matvec(P):
+            return sp_kernel_matvec(sd, sd, P, op=op, **params) + P * ridge
+        B = torch.stack([torch.as_tensor(y, dtype=torch.float64, device=sd.device),
+                         torch.ones(sd.shape[0], dtype=torch.float64, device=sd.device)], 1)
+        coeffs = []
+        Z = conjugate_gradient(None, B, tol=self.cg_tol, maxiter=self.cg_maxiter, matvec=matvec,
+                               coeffs=coeffs)
+        ok = bool(torch.isfinite(Z).all())
+        if ok:
+            ok = float((matvec(Z) - B).norm() / B.norm()) <= 1e-6
+        lo, hi = _ritz_range(coeffs, self.cg_tol) if ok else (ridge, ridge)
+        indefinite = lo - ridge < -_RITZ_TOL * hi
+        if indefinite or not ok:
+            what = (f"the kernel matrix is not positive semidefinite (the run saw an eigenvalue of "
+                    f"about {lo - ridge:.3g})" if indefinite else
+                    "K + I / penalty is not symmetric positive definite (or cg_maxiter is too "
+                    "small)")
+            raise ValueError(
+                f"matrix-free conjugate gradients refuse the {self.kernel!r} LS-SVM system: "
+                f"{what}, and its N x N matrix exceeds SQ_SVM_DENSE_BYTES, so there is no dense "
+                "fallback. Raise SQ_SVM_DENSE_BYTES or use algorithm='classic'.")
+        return self._cg_solution(Z)
+
+    @staticmethod
+    def _cg_solution(Z):
         eta, nu = Z[:, 0], Z[:, 1]
         b = float(eta.sum() / nu.sum())
         alpha = (eta - nu * b).cpu().numpy()
         return b, alpha
 
     def fit(self, X, y):
-        X, y = self._validate_data(X, y)
-        X = np.asarray(to_numpy(X), dtype=np.float64)
-        y = np.asarray(to_numpy(y), dtype=np.float64)
+        X, y = self._fit_input(X, y)
         self._gram_for_gamma(X)
         self.X = X
         if self.algorithm == "classic":
@@ -138,40 +322,51 @@ class LSSVC(_KernelMixin, ClassifierMixin, BaseEstimator):
             raise ValueError("Algorithm not implemented")
         self.b, self.alpha = self.b_, self.alpha_
         if self.kernel == "linear":
-            self.coef_ = self.alpha_ @ X
+            self.coef_ = self._xt(self.alpha_)
         self.classes_ = np.array([-1.0, 1.0])
         self.is_fitted_ = True
         return self
 
     def decision_function(self, X):
-        X = check_array(X)
+        X = self._check_queries(X)
         return self.get_h(X)
 
     def predict(self, X):
         return np.sign(self.decision_function(X))
 
     def get_P(self, X):
-        X = np.asarray(check_array(X), dtype=np.float64)
+        X = self._check_queries(X)
+        if not self._sparse_fit():
+            X = np.asarray(X, dtype=np.float64)
         N = self.X.shape[0]
         h = self.get_h(X)
-        Nu = self.b_ ** 2 + float(np.sum(self.alpha_ ** 2 * np.sum(self.X ** 2, 1)))
-        betas = np.sqrt((N * np.sum(X ** 2, 1) + 1) * Nu)
+        Nu = self.b_ ** 2 + float(np.sum(self.alpha_ ** 2 * self._train_row_sq()))
+        betas = np.sqrt((N * self._row_sq(X) + 1) * Nu)
         return 0.5 * (1 - h / betas), betas
 
 
-def conjugate_gradient(A, B, tol=1e-10, maxiter=1000):
-    """Batched CG for SPD A with several right-hand sides (columns of B)."""
+def conjugate_gradient(A, B, tol=1e-10, maxiter=1000, matvec=None, coeffs=None):
+    """Batched CG for SPD A with several right-hand sides (columns of B).
+    ``matvec``: a callable ``P -> A P`` used in place of the tensor ``A``;
+    ``coeffs``: a list that receives ``(alpha_k, beta_k, |r_k|^2 / |b|^2)`` of
+    every iteration: the step and direction coefficients and the relative
+    squared residual, one entry per column each."""
+    if matvec is None:
+        def matvec(P):
+            return A @ P
     X = torch.zeros_like(B)
-    R = B - A @ X
+    R = B - matvec(X)
     P = R.clone()
     rs = (R * R).sum(0)
     b2 = (B * B).sum(0).clamp(min=1e-300)
     for _ in range(maxiter):
-        AP = A @ P
+        AP = matvec(P)
         alpha = rs / (P * AP).sum(0).clamp(min=1e-300)
         X = X + P * alpha
         R = R - AP * alpha
         rs_new = (R * R).sum(0)
+        if coeffs is not None:
+            coeffs.append((alpha, rs_new / rs.clamp(min=1e-300), rs_new / b2))
         if bool((rs_new <= (tol ** 2) * b2).all()):
             break
         P = R + P * (rs_new / rs.clamp(min=1e-300))
@@ -244,9 +439,7 @@ class QLSSVC(_KernelMixin, ClassifierMixin, BaseEstimator):
         return float(sol[0]), sol[1:].cpu().numpy()
 
     def fit(self, X, y):
-        X, y = self._validate_data(X, y)
-        X = np.asarray(to_numpy(X), dtype=np.float64)
-        y = np.asarray(to_numpy(y), dtype=np.float64)
+        X, y = self._fit_input(X, y)
         self._gram_for_gamma(X)
         self.X = X
         N = X.shape[0]
@@ -255,10 +448,15 @@ class QLSSVC(_KernelMixin, ClassifierMixin, BaseEstimator):
         else:
             raise ValueError("Algorithm not implemented")
         self.b, self.alpha = self.b_, self.alpha_
-        self.alpha_F = math.sqrt(N) + self.penalty ** -1 + float(np.linalg.norm(X, ord="fro") ** 2)
-        self.Nu = self.b_ ** 2 + float(np.sum(self.alpha_ ** 2 * np.sum(X ** 2, 1)))
+        if sp.issparse(X):
+            xn = self._train_row_sq()
+            self.alpha_F = math.sqrt(N) + self.penalty ** -1 + float(xn.sum())
+            self.Nu = self.b_ ** 2 + float(np.sum(self.alpha_ ** 2 * xn))
+        else:
+            self.alpha_F = math.sqrt(N) + self.penalty ** -1 + float(np.linalg.norm(X, ord="fro") ** 2)
+            self.Nu = self.b_ ** 2 + float(np.sum(self.alpha_ ** 2 * np.sum(X ** 2, 1)))
         if self.kernel == "linear":
-            self.coef_ = self.alpha_ @ X
+            self.coef_ = self._xt(self.alpha_)
         self.classes_ = np.array([-1.0, 1.0])
         self.is_fitted_ = True
         self._calls = 0
@@ -305,12 +503,17 @@ class QLSSVC(_KernelMixin, ClassifierMixin, BaseEstimator):
     # ---------------------------------------------------------- predict
     def get_betas(self, X):
         check_is_fitted(self, "alpha_")
-        X = np.asarray(to_numpy(X), dtype=np.float64)
-        N = len(self.X)
-        return np.sqrt((N * np.sum(X ** 2, 1) + 1) * self.Nu)
+        if self._sparse_fit():
+            X = self._check_queries(X)
+        N = self.X.shape[0]
+        return np.sqrt((N * self._row_sq(X) + 1) * self.Nu)
 
     def get_h(self, X, approx=False):
-        hs = super().get_h(np.asarray(to_numpy(X), dtype=np.float64))
+        if self._sparse_fit():
+            X = self._check_queries(X)      # uploaded once for h and the betas
+            hs = super().get_h(X)
+        else:
+            hs = super().get_h(np.asarray(to_numpy(X), dtype=np.float64))
         if approx:
             betas = self.get_betas(X)
             if self.error_type == "absolute":
@@ -321,6 +524,8 @@ class QLSSVC(_KernelMixin, ClassifierMixin, BaseEstimator):
         return hs
 
     def get_P(self, X, approx=False):
+        if self._sparse_fit():
+            X = self._check_queries(X)
         hs = self.get_h(X)
         beta = self.get_betas(X)
         P = 0.5 * (1 - hs / beta)
@@ -334,7 +539,10 @@ class QLSSVC(_KernelMixin, ClassifierMixin, BaseEstimator):
 
     def predict(self, X):
         """+1 if the noisy P(x) <= 1/2 else -1 (``_qSVM.py:178-215``)."""
-        check_array(X)
+        if self._sparse_fit():
+            X = self._check_queries(X)
+        else:
+            check_array(X)
         check_is_fitted(self, "alpha_")
         P = self.get_P(X)
         betas = self.get_betas(X)
@@ -347,7 +555,10 @@ class QLSSVC(_KernelMixin, ClassifierMixin, BaseEstimator):
         return np.where(P <= 0.5, 1.0, -1.0)
 
     def classical_predict(self, X):
-        check_array(X)
+        if self._sparse_fit():
+            X = self._check_queries(X)
+        else:
+            check_array(X)
         return np.sign(self.get_h(X))
 
     def get_training_complexity(self):
@@ -370,7 +581,7 @@ class QLSSVC(_KernelMixin, ClassifierMixin, BaseEstimator):
             bound = self.relative_error * np.abs(self.get_h(x)) / beta
         bound = float(np.asarray(bound).reshape(-1)[0])
         approx = ba + self._noise(np.full(ba.shape, bound / np.sqrt(ba.size)))
-        return approx[0], approx[1:] @ self.X
+        return approx[0], self._xt(approx[1:])
 
     def get_all_attributes(self, X):
         betas = self.get_betas(X)

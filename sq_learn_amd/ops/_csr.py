@@ -3,7 +3,8 @@
 test, the chunk iterator of the torch twins, the pointer triple of a launch, the row-list
 normaliser, the squared row norms and the cached transpose.  The six modules
 import from here and not from each other (``sparse_radius`` also uses the
-k-NN operand object and epilogue).
+k-NN operand object and epilogue; ``sparse_kernel`` builds on that operand
+object and on the products of ``sparse_linalg``).
 """
 
 import torch

@@ -5,6 +5,8 @@
 Kernel matrices are one library GEMM (hipBLASLt via torch.matmul) plus an
 elementwise epilogue; distance matrices are chunked by the configured
 ``working_memory`` so 10^5 x 10^5 problems never materialise at once.
+The linear, polynomial, rbf and sigmoid kernels also take scipy sparse rows,
+which stay CSR (``ops/sparse_kernel.py``).
 """
 
 import numpy as np
@@ -37,7 +39,26 @@ def euclidean_distances(X, Y=None, *, squared=False, X_norm_squared=None, Y_norm
     return to_numpy(D) if numpy_in else D
 
 
+def _sparse_kernel(X, Y, kind, device=None, **params):
+    """A kernel matrix with scipy sparse ``X`` and / or ``Y`` as a numpy array:
+    both sides go to the device as CSR (a dense partner is converted) and
+    ``ops.sparse_kernel.sp_kernel_matrix`` forms K(X, Y); ``Y`` None or ``X``
+    itself is the self-join."""
+    import scipy.sparse as sp
+    from ..models._data import as_sparse_data
+    from ..ops.sparse_kernel import sp_kernel_matrix
+
+    def csr(A):
+        return A if sp.issparse(A) else sp.csr_matrix(np.asarray(to_numpy(A), dtype=np.float64))
+    dev = resolve_device(device)
+    qry = as_sparse_data(csr(X), dev)
+    fit = qry if Y is None or Y is X else as_sparse_data(csr(Y), dev)
+    return to_numpy(sp_kernel_matrix(fit, qry, kind, **params))
+
+
 def linear_kernel(X, Y=None, dense_output=True, device=None):
+    if _is_sparse(X) or _is_sparse(Y):
+        return _sparse_kernel(X, Y, "linear", device)
     numpy_in = not isinstance(X, torch.Tensor)
     X, Y = _pair(X, Y, device)
     K = X @ Y.T
@@ -45,6 +66,8 @@ def linear_kernel(X, Y=None, dense_output=True, device=None):
 
 
 def polynomial_kernel(X, Y=None, degree=3, gamma=None, coef0=1, device=None):
+    if _is_sparse(X) or _is_sparse(Y):
+        return _sparse_kernel(X, Y, "poly", device, gamma=gamma, coef0=coef0, degree=degree)
     numpy_in = not isinstance(X, torch.Tensor)
     X, Y = _pair(X, Y, device)
     if gamma is None:
@@ -54,6 +77,8 @@ def polynomial_kernel(X, Y=None, degree=3, gamma=None, coef0=1, device=None):
 
 
 def sigmoid_kernel(X, Y=None, gamma=None, coef0=1, device=None):
+    if _is_sparse(X) or _is_sparse(Y):
+        return _sparse_kernel(X, Y, "sigmoid", device, gamma=gamma, coef0=coef0)
     numpy_in = not isinstance(X, torch.Tensor)
     X, Y = _pair(X, Y, device)
     if gamma is None:
@@ -63,6 +88,8 @@ def sigmoid_kernel(X, Y=None, gamma=None, coef0=1, device=None):
 
 
 def rbf_kernel(X, Y=None, gamma=None, device=None):
+    if _is_sparse(X) or _is_sparse(Y):
+        return _sparse_kernel(X, Y, "rbf", device, gamma=gamma)
     numpy_in = not isinstance(X, torch.Tensor)
     X, Y = _pair(X, Y, device)
     if gamma is None:
