@@ -32,6 +32,57 @@ SQ_DEV double u01_53(const RngKey& key, unsigned long long ctr, int w) {
          (1.0 / 9007199254740992.0);
 }
 
+// ln pmf(x; n, pp) of the binomial law for integer 0 <= x <= n < 2^52 and
+// 0 < pp <= 1/2, in Loader's saddle-point form (C. Loader, "Fast and accurate
+// computation of binomial probabilities", 2000):
+//   -1/2 ln(2 pi x (n - x) / n) + se(n) - se(x) - se(n - x)
+//   - bd0(x, n pp) - bd0(n - x, n q),
+// se(x) = ln x! - ln(sqrt(2 pi x) (x / e)^x), bd0(x, M) = x ln(x / M) + M - x.
+// Every term keeps its relative precision (the deviation x - n pp comes from
+// one fma, exact up to its rounding), so the difference of two values is good
+// to a few ulps of the larger one for every n < 2^52; lgamma differences lose
+// n ln n * 2^-53, an error of order 1 at n ~ 1e14.
+__constant__ double kSferr[16] = {
+    0.0, 0.08106146679532725821967, 0.04134069595540929409382, 0.02767792568499833914879,
+    0.02079067210376509311152, 0.01664469118982119216319, 0.01387612882307074799875,
+    0.01189670994589177009506, 0.01041126526197209649748, 0.009255462182712732917729,
+    0.008330563433362871256469, 0.007573675487951840794972, 0.006942840107209529865664,
+    0.00640899418800420706844, 0.005951370112758847735624, 0.005554733551962801371039};
+
+SQ_DEV double stirlerr(double x) {
+  if (x <= 15.0) return kSferr[(int)x];
+  const double x2 = x * x;
+  return (1.0 / 12 - (1.0 / 360 - (1.0 / 1260 - (1.0 / 1680 - (1.0 / 1188) / x2) / x2) / x2) / x2) / x;
+}
+
+// x ln(x / M) + M - x for x > 0, given d = x - M to full relative precision
+SQ_DEV double bd0(double x, double M, double d) {
+  if (fabs(d) < 0.1 * (x + M)) {
+    double v = d / (x + M);
+    double s = d * v;
+    double ej = 2.0 * x * v;
+    v *= v;
+    for (int j = 1; j < 13; ++j) {
+      ej *= v;
+      const double s1 = s + ej / (double)(2 * j + 1);
+      if (s1 == s) break;
+      s = s1;
+    }
+    return s;
+  }
+  return x * log(x / M) - d;
+}
+
+SQ_DEV double log_pmf(double n, double pp, double x) {
+  if (x <= 0.0) return n * log1p(-pp);
+  if (x >= n) return n * log(pp);
+  const double d = __builtin_fma(-n, pp, x);        // x - n pp, one rounding
+  const double np = n * pp;
+  const double nq = __builtin_fma(-n, pp, n);
+  const double lead = 0.5 * log(6.283185307179586477 * x * ((n - x) / n));
+  return -lead + (stirlerr(n) - stirlerr(x) - stirlerr(n - x)) - bd0(x, np, d) - bd0(n - x, nq, -d);
+}
+
 // Binomial(n, p) with n < 2^52, p in [0, 1]; ctr selects an independent
 // stream of Philox blocks (2 uniforms per block).
 SQ_DEV double binomial(double n, double p, const RngKey& key, unsigned long long ctr) {
@@ -65,9 +116,8 @@ SQ_DEV double binomial(double n, double p, const RngKey& key, unsigned long long
     const double c = n * pp + 0.5;
     const double vr = 0.92 - 4.2 / b;
     const double alpha = (2.83 + 5.1 / b) * spq;
-    const double lpq = log(pp / q);
     const double m = floor((n + 1.0) * pp);
-    const double h = lgamma(m + 1.0) + lgamma(n - m + 1.0);
+    const double lfm = log_pmf(n, pp, m);
     k = c;
     // trial t uses Philox block (ctr << 6) + t: words (x, y) -> U, (z, w) -> V
     // (acceptance > 0.9 per trial: 63 trials are never exhausted in practice)
@@ -80,8 +130,10 @@ SQ_DEV double binomial(double n, double p, const RngKey& key, unsigned long long
       if (k < 0.0 || k > n) continue;
       if (us >= 0.07 && V <= vr) break;
       const double lv = log(V * alpha / (a / (us * us) + b));
-      if (lv <= h - lgamma(k + 1.0) - lgamma(n - k + 1.0) + (k - m) * lpq) break;
+      if (lv <= log_pmf(n, pp, k) - lfm) break;
     }
+    // 63 rejections (never in practice): the last proposal, inside the range
+    k = fmin(fmax(k, 0.0), n);
   }
   return flip ? n - k : k;
 }
