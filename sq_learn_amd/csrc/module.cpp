@@ -239,6 +239,13 @@ static PyMethodDef gram_methods[] = {
     SQ_FN(sp_gram_matvec, 0, "CSR x CSR kernel matrix applied to vectors, never formed"),
     {nullptr, nullptr, 0, nullptr}};
 
+// spmu.hip: the submodule ``_C.mu``.  Its format table is
+// tests/golden/native_formats_mu.json.
+static PyMethodDef mu_methods[] = {
+    SQ_FN(sp_mu_row_waves, VALUE, "row partials of the CSR mu(A) kernel"),
+    SQ_FN(sp_mu_sums, 0, "mu(A) power sums of a (centred) CSR matrix (fp64)"),
+    {nullptr, nullptr, 0, nullptr}};
+
 static struct PyModuleDef moddef ={PyModuleDef_HEAD_INIT, "_C",
                                     "sq_learn_amd native HIP kernels (gfx950)", -1, methods};
 static struct PyModuleDef lda_moddef = {PyModuleDef_HEAD_INIT, "sq_learn_amd._C.lda",
@@ -253,6 +260,9 @@ static struct PyModuleDef logistic_moddef = {PyModuleDef_HEAD_INIT, "sq_learn_am
 static struct PyModuleDef gram_moddef = {PyModuleDef_HEAD_INIT, "sq_learn_amd._C.gram",
                                          "sparse kernel-matrix kernels (spgram.hip)", -1,
                                          gram_methods};
+static struct PyModuleDef mu_moddef = {PyModuleDef_HEAD_INIT, "sq_learn_amd._C.mu",
+                                       "sparse mu(A) power-sum kernels (spmu.hip)", -1,
+                                       mu_methods};
 
 static bool add_submodule(PyObject* m, const char* name, PyModuleDef* def) {
   PyObject* sub = PyModule_Create(def);
@@ -268,7 +278,7 @@ PyMODINIT_FUNC PyInit__C(void) {
   if (!m) return nullptr;
   if (!add_submodule(m, "lda", &lda_moddef) || !add_submodule(m, "nmf", &nmf_moddef) ||
       !add_submodule(m, "logistic", &logistic_moddef) ||
-      !add_submodule(m, "gram", &gram_moddef)) {
+      !add_submodule(m, "gram", &gram_moddef) || !add_submodule(m, "mu", &mu_moddef)) {
     Py_DECREF(m);
     return nullptr;
   }

@@ -1,6 +1,6 @@
 // Wave-per-CSR-row helpers of the gather and scatter kernels: included by
 // csrc/spkmeans.hip (contiguous row ranges), csrc/spminibatch.hip (row lists),
-// csrc/spmm.hip (row segments), csrc/splda.hip, csrc/spnmf.hip and
+// csrc/spmm.hip and csrc/spmu.hip (row segments), csrc/splda.hip, csrc/spnmf.hip and
 // csrc/splogit.hip (one wave per row, two phases).  Placement rule: anything two sparse .hip
 // files need lives here - the readlane broadcast of a row's (col, v) pairs,
 // the row-gather accumulation and the tile walk around it, the fixed-point
@@ -29,6 +29,11 @@ SQ_DEV double bcast_d(double v, int q) {
 SQ_DEV double wave_min_d(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
+  return v;
+}
+SQ_DEV double wave_max_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
   return v;
 }
 SQ_DEV void sp_wave_sync() {

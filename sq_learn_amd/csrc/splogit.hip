@@ -39,12 +39,6 @@ namespace sq {
 
 constexpr int SP_LOGIT_SUM_THREADS = 1024;
 
-SQ_DEV double wave_max_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // exp out of line: inlined nine times, its constants fill the scalar registers of the multinomial
 // kernel past their limit
 static __device__ __attribute__((noinline)) double logit_exp(double x) { return exp(x); }

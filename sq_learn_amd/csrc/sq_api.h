@@ -124,6 +124,20 @@ SQ_API int sq_spmm(const void* indptr, const void* indices, const void* data, co
 SQ_API int sq_sp_row_moments(const void* indptr, const void* data, void* sum, void* sumsq,
                              long long n, void* stream);
 
+// spmu.hip (sq_sp_mu_row_waves: the rows of `part`, not an error code).  mu(A) power sums
+// of the CSR matrix (indptr, indices, data) [n, d] with the CSR of its transpose (tptr, tdata)
+// and that transpose's segment table: rowmax [nq], colsum [nq, d], q [nq] fp64, qstep > 0:
+// q is 0, qstep, 2 qstep, ...; mean [d] and base [nq] = sum_j |mean_j|^q (both or neither);
+// part [sq_sp_mu_row_waves(n), nq], scratch [slots of the table, nq]
+SQ_API int sq_sp_mu_row_waves(long long n);
+SQ_API int sq_sp_mu_sums(const void* indptr, const void* indices, const void* data,
+                         const void* tptr, const void* tdata, const void* seg_row,
+                         const void* seg_start, const void* seg_dst, long long nseg, int seg,
+                         const void* long_row, const void* long_ptr, long long nlong, long long n,
+                         long long d, const void* q, int nq, double qstep, const void* mean,
+                         const void* base, void* rowmax, void* colsum, void* part, void* scratch,
+                         void* stream);
+
 // spknn.hip (sq_sp_knn_tile_max: the tile size, not an error code)
 SQ_API int sq_sp_knn_tile_max();
 SQ_API int sq_sp_knn(const void* qptr, const void* qidx, const void* qval, const void* trow,

@@ -120,18 +120,17 @@ def prelude_stats(data: Data, mu_start=0.0, mu_end=1.0, mu_step=0.1, condition=T
     return eta, label, mu, cond
 
 
-def best_mu_distributed(data: Data, start=0.0, end=1.0, step=0.05, fro_sq=None, fro_sq_global=None,
-                        mean=None):
-    """``best_mu`` (``Utility.py:196-231``) over a row-sharded matrix: one
-    fused power-sum pass (row-max and column sums for every exponent of the
-    p-grid), then MAX / SUM all-reduces.  ``mean``: mu of the centred matrix
-    X - mean, subtracted inside the pass."""
+def _mu_grid(start, end, step):
+    """The p-grid of ``best_mu`` and the exponents 2p, 2(1 - p) its power sums need."""
     domain = [i for i in np.arange(start, end, step)] + [end]
     exps = sorted(set([round(float(2 * p), 12) for p in domain] +
                       [round(float(2 * (1 - p)), 12) for p in domain]))
-    rowmax, colsum = L.mu_power_sums_local(data.X, exps, mean=mean)
-    data.comm.all_reduce_(rowmax, op="max")
-    data.comm.all_reduce_(colsum, op="sum")
+    return domain, exps
+
+
+def _mu_search(domain, exps, rowmax, colsum):
+    """sqrt(s_2p(A) s_2(1-p)(A^T)) for every p of the grid and the position of
+    the smallest, from the (global) row maxima [nq] and column sums [nq, d]."""
     colmax = colsum.max(dim=1).values
     pos = {e: i for i, e in enumerate(exps)}
     vals = []
@@ -139,7 +138,20 @@ def best_mu_distributed(data: Data, start=0.0, end=1.0, step=0.05, fro_sq=None, 
         s1 = float(rowmax[pos[round(float(2 * p), 12)]])
         s2 = float(colmax[pos[round(float(2 * (1 - p)), 12)]])
         vals.append(float(np.sqrt(s1 * s2)))
-    best = int(np.argmin(vals))
+    return vals, int(np.argmin(vals))
+
+
+def best_mu_distributed(data: Data, start=0.0, end=1.0, step=0.05, fro_sq=None, fro_sq_global=None,
+                        mean=None):
+    """``best_mu`` (``Utility.py:196-231``) over a row-sharded matrix: one
+    fused power-sum pass (row-max and column sums for every exponent of the
+    p-grid), then MAX / SUM all-reduces.  ``mean``: mu of the centred matrix
+    X - mean, subtracted inside the pass."""
+    domain, exps = _mu_grid(start, end, step)
+    rowmax, colsum = L.mu_power_sums_local(data.X, exps, mean=mean)
+    data.comm.all_reduce_(rowmax, op="max")
+    data.comm.all_reduce_(colsum, op="sum")
+    vals, best = _mu_search(domain, exps, rowmax, colsum)
     if fro_sq_global is not None:
         fro = float(np.sqrt(fro_sq_global))
     else:
@@ -293,3 +305,26 @@ def as_sparse_data(X, device=None):
     return SparseData(torch.as_tensor(A.indptr.astype(np.int64)).to(dev),
                       torch.as_tensor(A.indices.astype(np.int32)).to(dev),
                       vals.to(dev).contiguous(), (n, d))
+
+
+def sparse_mean_var(sd):
+    """Column mean and (population) variance of a CSR matrix, fp64 [d] each,
+    from its column moments (``ops.sparse_linalg.sp_col_moments``)."""
+    from ..ops import sparse_linalg
+    s, ss = sparse_linalg.sp_col_moments(sd)
+    n = sd.shape[0]
+    mean = s / n
+    return mean, (ss / n - mean ** 2).clamp(min=0.0)
+
+
+def best_mu_sparse(sd, mean, start, end, step, fro_sq_global):
+    """:func:`best_mu_distributed` for the centred CSR matrix X - mean, which
+    is never formed (``ops.sparse_linalg.sp_mu_power_sums``)."""
+    from ..ops import sparse_linalg
+    domain, exps = _mu_grid(start, end, step)
+    rowmax, colsum = sparse_linalg.sp_mu_power_sums(sd, exps, mean=mean)
+    vals, best = _mu_search(domain, exps, rowmax, colsum)
+    fro = float(np.sqrt(fro_sq_global))
+    if vals[best] <= fro:
+        return f"p={domain[best]}", vals[best]
+    return "Frobenius", fro

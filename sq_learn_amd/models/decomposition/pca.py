@@ -15,12 +15,24 @@ from ...utils.extmath import stable_cumsum, _infer_dimension, fast_logdet, rando
 from ...utils.validation import check_is_fitted, seed_from_random_state
 from ...base import BaseEstimator, TransformerMixin
 from .._data import Data, as_data, as_sparse_data, global_mean_var
-from ._base import _BasePCA, _as_out
+from ._base import _BasePCA, _as_out, _stays_sparse, _SPARSE_DENSIFY_MAX
 from ._svd import full_svd, truncated_svd
 
 
 class PCA(_BasePCA):
-    """Principal component analysis (sklearn semantics)."""
+    """Principal component analysis (sklearn semantics).
+
+    ``scipy.sparse`` input of any format is accepted.  At most
+    ``_SPARSE_DENSIFY_MAX`` elements: densified, the fit of the same data as
+    an array.  Above: the rows stay CSR on the device and the centred
+    randomized SVD runs on them with the column mean as a rank-one term
+    (``svd_solver`` 'randomized', 'arpack', or 'auto' choosing it; an integer
+    ``n_components``); neither an n x d nor a d x d dense array is formed.
+    With l = n_components + 10 the peak extra device memory is the transposed
+    matrix (8 bytes per stored value), two n x l and one d x l fp64 blocks
+    and, for qPCA's mu(A), the nq x d column sums (nq = 11 exponents).
+    ``transform`` keeps sparse rows sparse whatever the fit saw; ``score`` and
+    ``score_samples`` need the d x d precision and refuse sparse input."""
 
     def __init__(self, n_components=None, *, copy=True, whiten=False, svd_solver="auto", tol=0.0,
                  iterated_power="auto", random_state=None, device=None):
@@ -48,6 +60,11 @@ class PCA(_BasePCA):
         return U
 
     def _fit(self, X):
+        if _stays_sparse(X):
+            _, _, _, U, S = self._fit_sparse(X)
+            return to_numpy(U), S
+        if sp.issparse(X):
+            X = X.toarray()        # small: the fit of the same data as an array
         data = as_data(X, device=self.device, copy=self.copy)
         self.n_features_in_ = data.d
         n_samples, n_features = data.n_global, data.d
@@ -117,6 +134,9 @@ class PCA(_BasePCA):
 
     def score_samples(self, X):
         check_is_fitted(self)
+        if sp.issparse(X):
+            raise TypeError("PCA.score_samples does not support sparse input: the precision "
+                            "matrix is n_features x n_features")
         X = np.asarray(to_numpy(X), dtype=np.float64)
         Xr = X - self.mean_
         precision = self.get_precision()
@@ -129,10 +149,6 @@ class PCA(_BasePCA):
 
     def _more_tags(self):
         return {"preserves_dtype": [np.float64, np.float32]}
-
-
-# sparse input of at most this many elements is densified (the exact branch)
-_SPARSE_DENSIFY_MAX = 4e6
 
 
 class TruncatedSVD(TransformerMixin, BaseEstimator):

@@ -28,19 +28,20 @@ import time
 import warnings
 
 import numpy as np
+import scipy.sparse as sp
 import torch
 
 from ...exceptions import ClassicalPathWarning
 from ...quantum import reference as Q
 from ...quantum.device import (gaussian_tomography, tomography_rows_torch, tomography_long,
                                consistent_phase_estimation_device)
-from ...runtime.device import to_numpy
+from ...runtime.device import to_numpy, resolve_device
 from ...runtime.rng import RngKey
 from ...utils.extmath import stable_cumsum, _infer_dimension, fast_logdet
 from ...utils.validation import check_is_fitted, seed_from_random_state
 from ...quantum import cost_model
-from .._data import as_data, global_mean_var, best_mu_distributed
-from ._base import _BasePCA, _as_out
+from .._data import as_data, global_mean_var, best_mu_distributed, best_mu_sparse
+from ._base import _BasePCA, _as_out, _stays_sparse
 from ._svd import full_svd, truncated_svd
 from ...ops import linalg as L
 
@@ -159,13 +160,10 @@ class QPCA(_BasePCA):
         self._knobs = dict(knobs)
 
     def _fit(self, X, knobs):
-        try:
-            import scipy.sparse as sp
-            if sp.issparse(X):
-                raise TypeError("PCA does not support sparse input. See TruncatedSVD for a "
-                                "possible alternative.")
-        except ImportError:  # pragma: no cover
-            pass
+        if _stays_sparse(X):
+            return self._fit_sparse_rows(X, knobs)
+        if sp.issparse(X):
+            X = X.toarray()        # small: the fit of the same data as an array
         data = as_data(X, device=self.device, copy=self.copy)
         self._store_knobs(knobs)
         self.n_features_in_ = data.d
@@ -336,6 +334,39 @@ class QPCA(_BasePCA):
                 self.norm_muA, self.muA = best_mu_distributed(data, start=0, end=1.0, step=0.1,
                                                               fro_sq_global=self.frob_norm ** 2,
                                                               mean=mean)
+            self._quantum_extras()
+        return self
+
+    def _fit_sparse_rows(self, X, knobs):
+        """``scipy.sparse`` rows above the densify limit (see ``PCA``): the
+        truncated fit on the centred randomized SVD of the CSR rows; with
+        ``quantum_truncated=True`` the quantum model runs unchanged on the
+        dense factors, mu(A) of the centred matrix from its stored entries
+        (``best_mu_sparse``, csrc/spmu.hip on the GPU)."""
+        self._store_knobs(knobs)
+        self.n_components_flag = self.n_components is not None
+        self.__dict__.pop("fit_phases_", None)
+        self._device_type = resolve_device(self.device).type
+        with self._phase("svd"):
+            sd, mean, total_var, U, S = self._fit_sparse(X, arpack_min_iter=7)
+        self._source_kind = "numpy"
+        self._comm = sd.comm
+        self._row_offset = 0
+        if not knobs.get("quantum_truncated"):
+            warnings.warn("Attention! This computational path is purely classic!",
+                          ClassicalPathWarning)
+        n_samples = sd.shape[0]
+        self.left_sv = to_numpy(U.T.contiguous())
+        self.spectral_norm = float(self.singular_values_[0])
+        self.scaled_singular_values = self.singular_values_ / self.spectral_norm
+        if knobs.get("quantum_truncated"):
+            self.frob_norm = float(np.sqrt(total_var.sum() * (n_samples - 1)))
+            self.all_components = self.components_
+            self.explained_variance_all = self.explained_variance_
+            self.explained_variance_ratio_all = self.explained_variance_ratio_
+            with self._phase("mu"):
+                self.norm_muA, self.muA = best_mu_sparse(sd, mean, start=0, end=1.0, step=0.1,
+                                                         fro_sq_global=self.frob_norm ** 2)
             self._quantum_extras()
         return self
 
@@ -630,10 +661,15 @@ class QPCA(_BasePCA):
         return super().inverse_transform(X, use_classical_components)
 
     def fit_transform(self, X, y=None, **quantum_kw):
+        if sp.issparse(X) and not _stays_sparse(X):
+            X = X.toarray()        # small: the array path for the fit and the projection
         return self.fit(X, **quantum_kw).transform(X)
 
     def score_samples(self, X):
         check_is_fitted(self)
+        if sp.issparse(X):
+            raise TypeError("QPCA.score_samples does not support sparse input: the precision "
+                            "matrix is n_features x n_features")
         X = np.asarray(to_numpy(X), dtype=np.float64)
         Xr = X - self.mean_
         n_features = X.shape[1]

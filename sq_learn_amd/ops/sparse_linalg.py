@@ -10,9 +10,11 @@ kernel on X, ``Z = X^T Y`` runs the same kernel on the CSR of X^T
 (``_csr.csr_transpose``, built once per matrix with torch plumbing and cached
 on the ``SparseData``), so both products are gathers: no floating-point
 atomics, results bit-identical from run to run and independent of the launch
-geometry.  A GPU input always takes the native path and raises when the
-extension is missing.  The torch twins (CPU) work in fp64 over densified row
-chunks, as ``ops/sparse_kmeans.py`` does.
+geometry.  ``sp_mu_power_sums`` (``csrc/spmu.hip``): the mu(A) power sums of
+the matrix centred by a column mean, as sums over the stored entries (PCA /
+qPCA on sparse rows).  A GPU input always takes the native path and raises
+when the extension is missing.  The torch twins (CPU) work in fp64 over
+densified row chunks, as ``ops/sparse_kmeans.py`` does.
 """
 
 import torch
@@ -64,31 +66,40 @@ def segments(sd, seg=None):
     return sd._segments[seg]
 
 
-def svd_bytes(sd, l, seg=None):
+def svd_bytes(sd, l, seg=None, centred=False, nq=0):
     """Device bytes a sparse randomized SVD with ``l`` range vectors keeps:
     X and X^T (values, indices, row pointers), their segment tables, one
     n x l and one d x l fp64 block and the scratch for long rows (at most
     nnz / seg + 1 partials beyond one per long row, bounded by 2 nnz / seg + 1
-    slots on either side)."""
+    slots on either side).  ``centred``: a second n x l block (the rank-one
+    terms are applied to the product before the next one reads it).  ``nq``:
+    the mu(A) pass of ``nq`` exponents on top (nq x d column sums, its
+    partials)."""
     seg = SEG_DEFAULT if seg is None else int(seg)
     n, d = sd.shape
     csr = 2 * sd.nnz * 8 + (n + d + 2) * 8
     tables = 3 * 8 * (n + d + 2 * (sd.nnz // seg + 1))
     scratch = (2 * sd.nnz // seg + 1) * l * 8
-    return csr + tables + (n + d) * l * 8 + scratch
+    extra = n * l * 8 if centred else 0
+    if nq:
+        extra += nq * 8 * (d + 8192 + 2 * sd.nnz // seg + 1)
+    return csr + tables + (n + d) * l * 8 + scratch + extra
 
 
-def check_svd_memory(sd, l, seg=None):
+def check_svd_memory(sd, l, seg=None, centred=False, nq=0):
     if sd.device.type != "cuda":
         return
     # X itself is already resident
-    need = svd_bytes(sd, l, seg) - (sd.nnz * 8 + (sd.shape[0] + 1) * 8)
+    need = svd_bytes(sd, l, seg, centred, nq) - (sd.nnz * 8 + (sd.shape[0] + 1) * 8)
     free = torch.cuda.mem_get_info(sd.device)[0]
     if need > free:
+        blocks = "two n x l blocks and a d x l fp64 block" if centred else \
+            "an n x l and a d x l fp64 block"
+        mu = f", the {nq} x d column sums of mu(A)" if nq else ""
         raise ValueError(f"sparse randomized SVD of a {sd.shape[0]} x {sd.shape[1]} matrix with "
                          f"{sd.nnz} stored values and {l} range vectors needs {need} more bytes "
-                         f"of device memory (the transposed matrix, an n x l and a d x l fp64 "
-                         f"block, the long-row scratch); {free} are free")
+                         f"of device memory (the transposed matrix, {blocks}, the long-row "
+                         f"scratch{mu}); {free} are free")
 
 
 # ---------------------------------------------------------------- products
@@ -192,3 +203,80 @@ def sp_col_moments_torch(sd):
         s.index_add_(0, c, v)
         ss.index_add_(0, c, v * v)
     return s, ss
+
+
+# ------------------------------------------------------------------ mu(A)
+def arithmetic_grid_step(exponents):
+    """b when the exponents are 0, b, 2b, ... (b > 0, the 2p of a p-grid; the
+    test of ``ops/linalg.mu_power_sums_local``), else 0.0."""
+    if len(exponents) >= 2 and exponents[0] == 0.0 and exponents[1] > 0.0:
+        b = float(exponents[1])
+        if all(abs(float(e) - i * b) <= 1e-9 * max(1.0, i * b) for i, e in enumerate(exponents)):
+            return b
+    return 0.0
+
+
+def sp_mu_power_sums(sd, exponents, mean=None, seg=None):
+    """(rowmax [nq], colsum [nq, d]) in fp64 of a = X - mean (``mean`` [d],
+    optional; a = X without it, where unstored entries contribute nothing):
+
+        rowmax[i] = max_r sum_j |a_rj|^q_i       colsum[i, j] = sum_r |a_rj|^q_i
+
+    with |0|^q = 0 for every q (q = 0 counts the nonzero a), the convention of
+    ``ops/linalg.mu_power_sums_local``.  The centred matrix is never formed:
+    csrc/spmu.hip sums over the stored entries (one pass over X, one over the
+    cached transpose; no atomics, bit-identical from run to run).  An
+    arithmetic exponent grid 0, b, 2b, ... takes its powers by products."""
+    n, d = sd.shape
+    exps = [float(e) for e in exponents]
+    nq = len(exps)
+    if nq < 1 or min(exps) < 0.0:
+        raise ValueError("mu(A) needs at least one exponent, none of them negative")
+    if mean is not None:
+        mean = mean.to(device=sd.device, dtype=torch.float64).reshape(-1).contiguous()
+        if mean.numel() != d:
+            raise ValueError(f"mean of {mean.numel()} values does not match a matrix with {d} "
+                             "columns")
+    if not native_ok(sd):
+        return sp_mu_power_sums_torch(sd, exps, mean)
+    dev = sd.device
+    t = csr_transpose(sd)
+    tab = segments(t, seg)
+    q = torch.tensor(exps, dtype=torch.float64, device=dev)
+    base = None
+    if mean is not None:
+        # sum_j |m_j|^q, the power sum of a row without stored entries
+        am = mean.abs()
+        nz = am != 0
+        lg = torch.log(torch.where(nz, am, torch.ones_like(am)))
+        base = torch.stack([nz.sum().double() if e == 0 else
+                            torch.where(nz, torch.exp(e * lg), torch.zeros_like(am)).sum()
+                            for e in exps])
+    rowmax = torch.empty(nq, dtype=torch.float64, device=dev)
+    colsum = torch.empty((nq, d), dtype=torch.float64, device=dev)
+    lib = nat.native().mu
+    part = torch.empty((lib.sp_mu_row_waves(n), nq), dtype=torch.float64, device=dev)
+    scratch = torch.empty((max(tab.slots, 1), nq), dtype=torch.float64, device=dev)
+    lib.sp_mu_sums(*csr_ptrs(sd), t.indptr.data_ptr(), t.data.data_ptr(), tab.row.data_ptr(),
+                   tab.start.data_ptr(), tab.dst.data_ptr(), tab.nseg, tab.seg,
+                   tab.long_row.data_ptr(), tab.long_ptr.data_ptr(), tab.nlong, n, d,
+                   q.data_ptr(), nq, arithmetic_grid_step(exps), nat.ptr(mean), nat.ptr(base),
+                   rowmax.data_ptr(), colsum.data_ptr(), part.data_ptr(), scratch.data_ptr(),
+                   nat.stream_handle(dev))
+    return rowmax, colsum
+
+
+def sp_mu_power_sums_torch(sd, exponents, mean=None):
+    """The dense law on densified row chunks: the fp64 branch of
+    ``ops/linalg.mu_power_sums_local`` chunk by chunk (no use of the
+    stored-entry identity of the kernel, which it is the reference for)."""
+    from .linalg import mu_power_sums_local
+    n, d = sd.shape
+    nq = len(exponents)
+    rowmax = torch.full((nq,), -float("inf"), dtype=torch.float64, device=sd.device)
+    colsum = torch.zeros((nq, d), dtype=torch.float64, device=sd.device)
+    for a, b in chunks(n, TWIN_CHUNK):
+        rm, cs = mu_power_sums_local(sd.dense_rows(a, b), list(exponents), mean=mean)
+        rowmax = torch.maximum(rowmax, rm)
+        colsum += cs
+    return rowmax, colsum

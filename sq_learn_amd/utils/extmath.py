@@ -272,16 +272,36 @@ def _rsvd_finish(Y, B, k, comm, flip_sign):
     return U, sv[:k].to(dev), Vt
 
 
+def _sp_centred_xw(sd, Z, mean):
+    """(X - 1 mean^T) Z = X Z - 1 (mean^T Z): the sparse product and a
+    rank-one term on the n x l block (fp64)."""
+    from ..ops import sparse_linalg as S
+    Y = S.sp_xw(sd, Z)
+    Y -= mean @ Z
+    return Y
+
+
+def _sp_centred_xty(sd, Y, mean):
+    """(X - 1 mean^T)^T Y = X^T Y - mean (1^T Y), on the d x l block (fp64)."""
+    from ..ops import sparse_linalg as S
+    Zn = S.sp_xty(sd, Y)
+    Zn -= torch.outer(mean, Y.sum(0))
+    return Zn
+
+
 def randomized_svd_sparse(sd, n_components, *, n_oversamples=10, n_iter="auto", seed=0,
-                          flip_sign=True):
-    """Randomized SVD of a CSR matrix (``models._data.SparseData``, no
-    centring): the "stream" iteration of :func:`randomized_svd_distributed`
-    with its three passes over the rows replaced by the sparse products of
+                          flip_sign=True, mean=None):
+    """Randomized SVD of a CSR matrix (``models._data.SparseData``): the
+    "stream" iteration of :func:`randomized_svd_distributed` with its three
+    passes over the rows replaced by the sparse products of
     ``ops/sparse_linalg.py`` (csrc/spmm.hip on the GPU) - X Z, X^T Y and
     X^T (X Z).  The same Philox test matrix, the same host QR per power
     iteration, the same two CholeskyQR passes on the dense Y, the same small
     SVD and sign rule, so on equal data it agrees with the dense path to
-    rounding.  Returns (U [n, k] fp64, s [k], Vt [k, d])."""
+    rounding.  ``mean`` ([d], optional): the SVD of the centred matrix
+    X - 1 mean^T, which is never formed - every product gets its rank-one
+    term on the dense n x l / d x l block.  Returns (U [n, k] fp64, s [k],
+    Vt [k, d])."""
     from ..ops import sparse_linalg as S
     from ..ops.random import philox_normal
     from ..runtime.rng import RngKey
@@ -291,12 +311,20 @@ def randomized_svd_sparse(sd, n_components, *, n_oversamples=10, n_iter="auto", 
     if n_iter == "auto":
         n_iter = 7 if k < 0.1 * min(n, d) else 4
     dev = sd.device
-    S.check_svd_memory(sd, l)
+    S.check_svd_memory(sd, l, centred=mean is not None)
     Z = philox_normal((d, l), RngKey(seed, "gaussian", 0), dtype=torch.float64, device="cpu")
+    if mean is None:
+        for _ in range(n_iter):
+            Z, _ = torch.linalg.qr(S.sp_power_iter(sd, Z.to(dev)).cpu())
+        Y = _cholqr2_rows(S.sp_xw(sd, Z.to(dev)), sd.comm)
+        B = S.sp_xty(sd, Y).cpu().T
+        return _rsvd_finish(Y, B, k, sd.comm, flip_sign)
+    mean = mean.to(device=dev, dtype=torch.float64)
     for _ in range(n_iter):
-        Z, _ = torch.linalg.qr(S.sp_power_iter(sd, Z.to(dev)).cpu())
-    Y = _cholqr2_rows(S.sp_xw(sd, Z.to(dev)), sd.comm)
-    B = S.sp_xty(sd, Y).cpu().T
+        Zn = _sp_centred_xty(sd, _sp_centred_xw(sd, Z.to(dev), mean), mean)
+        Z, _ = torch.linalg.qr(Zn.cpu())
+    Y = _cholqr2_rows(_sp_centred_xw(sd, Z.to(dev), mean), sd.comm)
+    B = _sp_centred_xty(sd, Y, mean).cpu().T
     return _rsvd_finish(Y, B, k, sd.comm, flip_sign)
 
 
