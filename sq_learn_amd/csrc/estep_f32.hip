@@ -2153,9 +2153,13 @@ __global__ void __launch_bounds__(256, DX <= 256 ? 3 : 1) gap_screen_kernel(
 // The gap screen's shift operands after the update c(t) -> c(t+1): for every
 // ring slot s whose base iteration b (s = b % ring) can still be current at
 // the next E-step (bit s of `valid`), per centroid j (one wave) the
-// accumulated shift S_j = c_j(t+1) - c_j(b) in fp64 (exact: fp32 inputs),
-// fp16 S~_j = rn(beta_j S_j) with beta_j a power of two putting max|S_j| near
-// 2^14, and dq[s][j] = {q_j = |c_j(t+1)|^2 - |c_j(b)|^2 (fp32), its error
+// accumulated shift S_j = c_j(t+1) - c_j(b) in fp64 (exact while the
+// exponents of the two fp32 values are at most 2^29 apart per coordinate;
+// beyond that it carries a 2^-53 relative error, far below the fp16 error e_j
+// measures), fp16 S~_j = rn16(rn32(beta_j S_j)) with beta_j a power of two
+// putting max|S_j| in [2^13, 2^14) (a coordinate below 2^-38 of it has a zero
+// image, from 2^-28 down a subnormal one), and
+// dq[s][j] = {q_j = |c_j(t+1)|^2 - |c_j(b)|^2 (fp32), its error
 // bound, |S_j| (rounded up), e_j = |S_j - S~_j / beta_j| (rounded up),
 // 1 / (alpha beta_j), 0, 0, 0}.  c(b) comes from the snapshot ring; slot
 // `snew` (b = t) takes c(t) itself, which the kernel also snapshots.  Padded
@@ -2185,7 +2189,13 @@ __global__ void __launch_bounds__(256) shift_operand_kernel(
     const float a32 = f < d ? co[f] : 0.0f;
     const double a = (double)a32, b = f < d ? (double)cn[f] : 0.0;
     const double sft = b - a;
-    const _Float16 h = (_Float16)(float)(beta * sft);
+    // two roundings, fp64 -> fp32 -> fp16, as written: left to itself hipcc
+    // folds the two casts into ONE software fp64 -> fp16 conversion (~40
+    // integer instructions per element, and another value at a double-rounding
+    // tie); opaque in between, they are the two hardware conversions
+    float s32 = (float)(beta * sft);
+    asm volatile("" : "+v"(s32));
+    const _Float16 h = (_Float16)s32;
     dsh[rs * d_pad + f] = h;
     if (fresh) sn[f] = a32;
     const double r = sft - (double)h / beta;
